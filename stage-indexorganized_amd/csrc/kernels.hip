@@ -18,6 +18,9 @@
 //     Iterator::GetNext (b_tree.h:899-941).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "kernel_api.hpp"
 #include "stage_core.hpp"
 #include "visibility.hpp"
@@ -230,6 +233,17 @@ __global__ __launch_bounds__(256) void resolve_kernel(DevTable t, const uint64_t
 // ----------------------------------------------------------------------------------------
 // point probe
 
+// a slot's two 16-B words as a probe candidate reads them (SlotInfo without the padding)
+struct SlotWords {
+    uint64_t okey, meta;
+    uint32_t next, image;
+};
+__device__ __forceinline__ SlotWords slot_words(const SlotInfo *p) {
+    const u32x4 *w = reinterpret_cast<const u32x4 *>(p);
+    const u32x4 w0 = w[0], w1 = w[1];
+    return SlotWords{((uint64_t)w0.y << 32) | w0.x, ((uint64_t)w0.w << 32) | w0.z, w1.x, w1.y};
+}
+
 // 16-B output store at base + off (base wave-uniform).  POL 0: temporal; 1: nontemporal (the
 // line is still kept in the XCD's L2); 2: write-through (sc1 buffer store: the line leaves L2,
 // so the output stream does not evict cached rows, heads and separator nodes --
@@ -250,8 +264,9 @@ __device__ __forceinline__ void st16(u32x4 v, uint8_t *base, uint32_t off) {
     }
 }
 
-// CH: probes per wave chunk (64; 16 for small batches of the one-probe-in-flight instances, so
-// that a wave's chunk is not a chain of 64 dependent probes while most of the chip idles).
+// Point probes of 8-byte and variable-length keys in leaves of 64 / 128 slots, a wave per chunk
+// of 64 probes, G probes in flight per wave (wide keys and larger leaves: probe_lane_kernel /
+// probe_split_kernel).
 // ST: status record bytes -- 32 (stage_probe_out) or 16 (stage_probe_out16, opt-in: status |
 // flags | hops, cstamp, copy_sstamp, rec_cstamp -- what IndexScanExecutor and PerformRead use)
 // FAN: fan-out probes (the sharded front-end's coalesced requests, dist.hip): probe i's status
@@ -259,8 +274,7 @@ __device__ __forceinline__ void st16(u32x4 v, uint8_t *base, uint32_t off) {
 // the positions k themselves; fan null: {i, i + 1}, probe i's one position flist[i]) instead of
 // position i -- the row leaves registers once per caller and no second pass copies it (rows of
 // at most 1024 B, recs required).
-template <bool VARLEN, int SPL, int G, int POL = 1, int KW = 1, int CH = 64, int ST = 32, bool FAN = false,
-          bool DEST = false>
+template <bool VARLEN, int SPL, int G, int POL = 1, int ST = 32, bool FAN = false, bool DEST = false>
 __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *__restrict__ keys,
                                                     const uint16_t *__restrict__ lens,
                                                     const uint32_t *__restrict__ rids,
@@ -287,9 +301,12 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     const uint32_t out_chunks = t.stride >> 4;
-    for (uint64_t base = wave * CH; base < n; base += nwaves * CH) {
+    for (uint64_t base = wave * 64; base < n; base += nwaves * 64) {
         const uint64_t i = base + lane;
-        const bool valid = lane < (uint32_t)CH && i < n;
+        // lane < 64 always holds; without it hipcc allocates probe_kernel's registers differently
+        // (<true, 2, 4>: 93 VGPRs instead of 94, fewer SGPR spills), which would have to be
+        // re-timed: kept so that the instances are the measured ones, instruction for instruction
+        const bool valid = lane < 64u && i < n;
         u32x4 my_a = u32x4{0, 0, 0, 0}, my_b = u32x4{0, 0, 0, 0};  // this lane's probe result
         const uint32_t len = t.key_width ? t.key_width : (lens && valid ? (uint32_t)lens[i] : 8u);
         const uint32_t rid = rids ? (valid ? rids[i] : 0u) : 0xFFFFFFFEu;
@@ -302,13 +319,13 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
             my_o = (uint64_t)s_dout[sg];
             my_r = (uint64_t)s_drec[sg];
         }
-        uint64_t ok[KW];
-        load_okey<KW>(keys, i, valid, len, ok);
+        uint64_t ok;
+        load_okey<1>(keys, i, valid, len, &ok);
         uint32_t leaf = 0;
-        if (valid) leaf = leaf_in ? leaf_in[i] : resolve_leaf<VARLEN, KW>(t, ok, len, true);
+        if (valid) leaf = leaf_in ? leaf_in[i] : resolve_leaf<VARLEN, 1>(t, &ok, len, true);
         if (leaf > t.nseps) leaf = t.nseps;  // host-supplied ids are clamped to the table
-        const int cnt = (int)((n - base) < CH ? (n - base) : CH);
-        // one probe in flight (G = 1: the wide-key and large-leaf instances): the next probe's
+        const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
+        // one probe in flight (G = 1, stage_set_probe_tuning only): the next probe's
         // fingerprint bytes load while this one runs, so a probe exposes one dependent round
         // trip (its candidates' slot words) instead of two
         constexpr bool PFH = G == 1;
@@ -320,7 +337,7 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
         }
         for (int j0 = 0; j0 < cnt; j0 += G) {
             uint32_t lf[G], rd[G], xl[G];
-            uint64_t x[G][KW];
+            uint64_t x[G];
             uint32_t fpb[G][SPL];
             // phase 1: leaf heads of G probes -- the fingerprint bytes only: an empty or
             // invisible slot holds fingerprint 0, which no key has (key_fp_words), so the
@@ -330,8 +347,7 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
                 const int j = j0 + g < cnt ? j0 + g : cnt - 1;
                 lf[g] = rl32(leaf, j);
                 rd[g] = rl32(rid, j);
-#pragma unroll
-                for (int w = 0; w < KW; ++w) x[g][w] = rl64(ok[w], j);
+                x[g] = rl64(ok, j);
                 xl[g] = VARLEN ? rl32(len, j) : t.key_width;
                 if (PFH) {
 #pragma unroll
@@ -353,7 +369,7 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
             bool cand[G][SPL];
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const uint32_t fx = key_fp_words(x[g], KW);
+                const uint32_t fx = key_fp_words(&x[g], 1);
 #pragma unroll
                 for (int s = 0; s < SPL; ++s) {
                     cand[g][s] = fpb[g][s] == fx;
@@ -362,28 +378,11 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
                     wnext[g][s] = 0;
                     wimg[g][s] = 0;
                     if (cand[g][s]) {
-                        const u32x4 *w = reinterpret_cast<const u32x4 *>(t.slot + (uint64_t)lf[g] * t.cap + s * 64 + lane);
-                        const u32x4 w0 = w[0], w1 = w[1];
-                        // the other key words load with the slot word (one round trip) in leaves
-                        // of up to 4 slot groups; larger leaves load them after the order-key
-                        // match (fewer registers in flight)
-                        constexpr bool COK = SPL <= 4;
-                        uint64_t kw[KW > 1 ? KW : 1];
-#pragma unroll
-                        for (int w = 1; w < KW; ++w)
-                            kw[w] = COK ? t.okey[((uint64_t)lf[g] * KW + w) * t.cap + s * 64 + lane] : 0ull;
-                        wok[g][s] = ((uint64_t)w0.y << 32) | w0.x;
-                        wmeta[g][s] = ((uint64_t)w0.w << 32) | w0.z;
-                        wnext[g][s] = w1.x;
-                        wimg[g][s] = w1.y;
-                        if (KW > 1 && wok[g][s] == x[g][0]) {  // confirm the other key words
-                            bool eq = true;
-#pragma unroll
-                            for (int w = 1; w < KW; ++w)
-                                eq = eq && (COK ? kw[w] : t.okey[((uint64_t)lf[g] * KW + w) * t.cap + s * 64 + lane]) ==
-                                               x[g][w];
-                            if (!eq) wok[g][s] = ~x[g][0];
-                        }
+                        const SlotWords w = slot_words(t.slot + (uint64_t)lf[g] * t.cap + s * 64 + lane);
+                        wok[g][s] = w.okey;
+                        wmeta[g][s] = w.meta;
+                        wnext[g][s] = w.next;
+                        wimg[g][s] = w.image;
                     }
                 }
             }
@@ -396,7 +395,7 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
                 uint32_t nx = 0, im = 0;
 #pragma unroll
                 for (int s = SPL - 1; s >= 0; --s) {
-                    const bool hitl = cand[g][s] && wok[g][s] == x[g][0] && (!VARLEN || meta_keylen(wmeta[g][s]) == xl[g]);
+                    const bool hitl = cand[g][s] && wok[g][s] == x[g] && (!VARLEN || meta_keylen(wmeta[g][s]) == xl[g]);
                     const uint64_t hit = ballot(hitl);
                     if (hit) {
                         const int b = __builtin_ctzll(hit);
@@ -546,6 +545,8 @@ __device__ __forceinline__ void ring_probe_one(const DevTable &t, uint32_t lane,
         uint64_t wok = 0, wmeta = 0;
         uint32_t wnext = 0, wimg = 0, wloc = 0;
         if (cand) {
+            // unpacked here, not through slot_words(): with it hipcc numbers the reader's
+            // registers differently (same counts), and the reader is timed separately
             const u32x4 *w = reinterpret_cast<const u32x4 *>(t.slot + (uint64_t)lf * t.cap + s * 64 + lane);
             const u32x4 w0 = w[0], w1 = w[1];
             wok = ((uint64_t)w0.y << 32) | w0.x;
@@ -1140,9 +1141,9 @@ __global__ __launch_bounds__(64) void scan_pair_compact_kernel(DevTable t0, DevT
 // (FirstPrefixSink); img_out[i] / st_out[i] = that tuple's heap row and status.
 constexpr int kFirstChunk = 16;
 constexpr uint8_t kFirstUndecided = 0xFE;  // scan_first_split_kernel -> scan_first_rest_kernel
-// Point probes of the one-probe-in-flight instances (fixed-width keys of 9..32 bytes, or
-// 8-byte keys in leaves above 128 slots) in two stages per chunk of CH probes -- the results of
-// probe_kernel<false, SPL, 1, .., KW, CH>:
+// Point probes of the tables probe_kernel does not serve (fixed-width keys of 9..32 bytes, or
+// 8-byte keys in leaves above 128 slots) in two stages per chunk of CH probes (4 / 16 / 64 by
+// batch size, launch_probe) -- probe_kernel's results:
 //  A (wave per probe, in turn): the leaf head's fingerprint bytes (the next 4 probes' in flight
 //    while this one runs -- the next one only for leaves above 256 slots, whose larger heads
 //    would cost occupancy), one ballot per slot group, and the candidate slots in slot order
@@ -1154,6 +1155,58 @@ constexpr uint8_t kFirstUndecided = 0xFE;  // scan_first_split_kernel -> scan_fi
 //    of one probe's at a time.
 //  Rows (if requested) are then copied wave-wide, probe by probe, as probe_kernel's phase 4.
 constexpr int kProbeCand = 8;
+
+// ---- steps shared by probe_split_kernel and probe_lane_kernel (fixed-width keys, a lane per
+// probe of the wave's chunk).  The chunk prologue (device batch size, wave position, read id,
+// key words, leaf clamp) is written out in both: as a helper it changes the code hipcc
+// generates for all of their instances, down to how blockDim is read, for six lines saved.
+
+// slot sl of the probe's leaf (first slot lb = leaf * cap) against its key: the slot word's
+// order key, then the other key words (okey planes).  A match sets slot / m / nx / im
+// (visibility()'s arguments).
+template <int KW>
+__device__ __forceinline__ bool confirm_slot(const DevTable &t, uint32_t leaf, uint64_t lb, uint32_t sl,
+                                             const uint64_t *ok, int &slot, uint64_t &m, uint32_t &nx,
+                                             uint32_t &im) {
+    const SlotWords w = slot_words(t.slot + lb + sl);
+    bool eq = w.okey == ok[0];
+#pragma unroll
+    for (int k = 1; k < KW; ++k) eq = eq && t.okey[((uint64_t)leaf * KW + k) * t.cap + sl] == ok[k];
+    if (eq) {
+        slot = (int)sl;
+        m = w.meta;
+        nx = w.next;
+        im = w.image;
+    }
+    return eq;
+}
+
+// the chunk's output: the rows (if requested) wave-wide, probe by probe (lane j holds probe
+// base + j's result, cnt probes), then every probe's 32-B status record from its lane
+__device__ __forceinline__ void store_chunk(const DevTable &t, uint32_t lane, uint64_t base, int cnt, bool valid,
+                                            uint32_t leaf, const ProbeRes &r, stage_probe_out_dev *out,
+                                            uint8_t *recs, uint32_t out_chunks) {
+    if (recs) {
+        for (int j = 0; j < cnt; ++j) {
+            const uint32_t img = rl32(r.image, j);
+            for (uint32_t c0 = 0; c0 < out_chunks; c0 += 64) {
+                const uint32_t c = c0 + lane;
+                if (c >= out_chunks) continue;
+                u32x4 v = u32x4{0, 0, 0, 0};
+                if (img != 0xFFFFFFFFu) v = heap_chunk(t, img, c);
+                st16<1>(v, recs + (base + j) * (uint64_t)t.stride, c * 16u);
+            }
+        }
+    }
+    if (valid) {
+        u32x4 a, b;
+        pack_out(leaf, r, a, b);
+        uint8_t *ob = reinterpret_cast<uint8_t *>(out + base);
+        st16<1>(a, ob, lane * 32u);
+        st16<1>(b, ob, lane * 32u + 16u);
+    }
+}
+
 template <int SPL, int KW, int CH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void probe_split_kernel(DevTable t, const uint64_t *__restrict__ keys,
                                                           const uint32_t *__restrict__ rids,
@@ -1227,51 +1280,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void p
         uint32_t nx = 0, im = 0;
         if (valid) {
             const uint64_t lb = (uint64_t)leaf * t.cap;
-            auto confirm = [&](uint32_t sl) {
-                const u32x4 *w = reinterpret_cast<const u32x4 *>(t.slot + lb + sl);
-                const u32x4 w0 = w[0], w1 = w[1];
-                bool eq = (((uint64_t)w0.y << 32) | w0.x) == ok[0];
-#pragma unroll
-                for (int k = 1; k < KW; ++k) eq = eq && t.okey[((uint64_t)leaf * KW + k) * t.cap + sl] == ok[k];
-                if (eq) {
-                    slot = (int)sl;
-                    m = ((uint64_t)w0.w << 32) | w0.z;
-                    nx = w1.x;
-                    im = w1.y;
-                }
-                return eq;
-            };
             if (my_nc <= (uint32_t)kProbeCand) {
                 for (uint32_t c = 0; c < my_nc; ++c)
-                    if (confirm(s_cand[wv][lane][c])) break;
+                    if (confirm_slot<KW>(t, leaf, lb, s_cand[wv][lane][c], ok, slot, m, nx, im)) break;
             } else {  // more candidates than the list holds: walk the head in slot order
                 const uint8_t *h = t.head + (uint64_t)leaf * t.head_bytes;
                 for (uint32_t sl = 0; sl < t.cap; ++sl)
-                    if (h[sl] == fx_mine && confirm(sl)) break;
+                    if (h[sl] == fx_mine && confirm_slot<KW>(t, leaf, lb, sl, ok, slot, m, nx, im)) break;
             }
         }
         ProbeRes r;
         visibility(t, slot, m, nx, im, rid, r);
-        // rows: wave-wide, probe by probe
-        if (recs) {
-            for (int j = 0; j < cnt; ++j) {
-                const uint32_t img = rl32(r.image, j);
-                for (uint32_t c0 = 0; c0 < out_chunks; c0 += 64) {
-                    const uint32_t c = c0 + lane;
-                    if (c >= out_chunks) continue;
-                    u32x4 v = u32x4{0, 0, 0, 0};
-                    if (img != 0xFFFFFFFFu) v = heap_chunk(t, img, c);
-                    st16<1>(v, recs + (base + j) * (uint64_t)t.stride, c * 16u);
-                }
-            }
-        }
-        if (valid) {
-            u32x4 a, b;
-            pack_out(leaf, r, a, b);
-            uint8_t *ob = reinterpret_cast<uint8_t *>(out + base);
-            st16<1>(a, ob, lane * 32u);
-            st16<1>(b, ob, lane * 32u + 16u);
-        }
+        store_chunk(t, lane, base, cnt, valid, leaf, r, out, recs, out_chunks);
         __builtin_amdgcn_wave_barrier();  // s_cand is rewritten by the next chunk
     }
 }
@@ -1352,7 +1372,7 @@ __global__ __launch_bounds__(256) void probe_lane_kernel(DevTable t, const uint6
     static_assert(SPL <= 4, "head of at most 256 slots in registers");
     __shared__ uint64_t s_x[4][64 * KW];
     __shared__ uint32_t s_node[4][64];
-    if (dn) n = *dn < n ? *dn : n;
+    if (dn) n = *dn < n ? *dn : n;  // the batch's size as a previous kernel left it (launched for n at most)
     const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
@@ -1399,20 +1419,7 @@ __global__ __launch_bounds__(256) void probe_lane_kernel(DevTable t, const uint6
         uint64_t m = 0;
         uint32_t nx = 0, im = 0;
         const uint64_t lb = (uint64_t)leaf * t.cap;
-        auto confirm = [&](uint32_t sl) {
-            const u32x4 *w = reinterpret_cast<const u32x4 *>(t.slot + lb + sl);
-            const u32x4 w0 = w[0], w1 = w[1];
-            bool eq = (((uint64_t)w0.y << 32) | w0.x) == ok[0];
-#pragma unroll
-            for (int k = 1; k < KW; ++k) eq = eq && t.okey[((uint64_t)leaf * KW + k) * t.cap + sl] == ok[k];
-            if (eq) {
-                slot = (int)sl;
-                m = ((uint64_t)w0.w << 32) | w0.z;
-                nx = w1.x;
-                im = w1.y;
-            }
-            return eq;
-        };
+        auto confirm = [&](uint32_t sl) { return confirm_slot<KW>(t, leaf, lb, sl, ok, slot, m, nx, im); };
         // rounds: every lane still looking confirms its next candidate, the loads together
         if (nc > 0) confirm(c0);
         if (slot < 0 && nc > 1) confirm(c1);
@@ -1431,26 +1438,7 @@ __global__ __launch_bounds__(256) void probe_lane_kernel(DevTable t, const uint6
                 visibility(t, slot, m, nx, im, mrids[q], rq);
                 if (rq.status != ST_LATEST && rq.status != ST_COPY && rq.status != ST_OLD) atomicOr(missed + q, 1);
             }
-        if (recs) {  // rows: wave-wide, probe by probe
-            const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
-            for (int j = 0; j < cnt; ++j) {
-                const uint32_t img = rl32(r.image, j);
-                for (uint32_t cc0 = 0; cc0 < out_chunks; cc0 += 64) {
-                    const uint32_t c = cc0 + lane;
-                    if (c >= out_chunks) continue;
-                    u32x4 v = u32x4{0, 0, 0, 0};
-                    if (img != 0xFFFFFFFFu) v = heap_chunk(t, img, c);
-                    st16<1>(v, recs + (base + j) * (uint64_t)t.stride, c * 16u);
-                }
-            }
-        }
-        if (valid) {
-            u32x4 a, b;
-            pack_out(leaf, r, a, b);
-            uint8_t *ob = reinterpret_cast<uint8_t *>(out + base);
-            st16<1>(a, ob, lane * 32u);
-            st16<1>(b, ob, lane * 32u + 16u);
-        }
+        store_chunk(t, lane, base, (int)((n - base) < 64 ? (n - base) : 64), valid, leaf, r, out, recs, out_chunks);
     }
 }
 
@@ -1939,13 +1927,44 @@ static int grid_for(uint64_t waves_needed, int waves_per_block, int max_blocks) 
     return (int)b;
 }
 
+// grid cap of the probe and scan launchers unless the tuning struct (ProbeTuning / ScanTuning) sets one
+constexpr int kDefaultMaxBlocks = 16384;
+template <class Tuning>
+static int max_blocks(const Tuning &tune) { return tune.max_blocks > 0 ? tune.max_blocks : kDefaultMaxBlocks; }
+
+// Geometry dispatch, the one place a table's run-time shape becomes template arguments:
+// f(S) / f(KW) / f(S, KW) is called with std::integral_constant values, S = slot groups per leaf
+// (cap / 64: 1, 2, 4, 8 or 16 -- HostTable admits no other capacity) and KW = order words per
+// key (1, 2 or 4, table_key_words).  A launcher that has no kernel for part of the range
+// guards it with `if constexpr`, so the lambda instantiates exactly the kernels it can launch.
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <class F>
+static void with_slot_groups(const DevTable &t, F &&f) {
+    switch (t.cap / 64) {
+        case 1: f(int_c<1>()); break;
+        case 2: f(int_c<2>()); break;
+        case 4: f(int_c<4>()); break;
+        case 8: f(int_c<8>()); break;
+        default: f(int_c<16>()); break;
+    }
+}
+template <class F>
+static void with_key_words(const DevTable &t, F &&f) {
+    if (t.key_words == 4) f(int_c<4>());
+    else if (t.key_words == 2) f(int_c<2>());
+    else f(int_c<1>());
+}
+template <class F>
+static void with_geometry(const DevTable &t, F &&f) {
+    with_key_words(t, [&](auto KW) { with_slot_groups(t, [&](auto S) { f(S, KW); }); });
+}
+
 hipError_t launch_resolve(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n, int le_child,
                           uint32_t *out, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const unsigned b = (unsigned)((n + 255) / 256);
-    if (t.key_words == 4) resolve_kernel<4><<<b, 256, 0, s>>>(t, keys, lens, n, le_child, out);
-    else if (t.key_words == 2) resolve_kernel<2><<<b, 256, 0, s>>>(t, keys, lens, n, le_child, out);
-    else resolve_kernel<1><<<b, 256, 0, s>>>(t, keys, lens, n, le_child, out);
+    with_key_words(t, [&](auto KW) { resolve_kernel<KW()><<<b, 256, 0, s>>>(t, keys, lens, n, le_child, out); });
     return hipGetLastError();
 }
 
@@ -1958,13 +1977,13 @@ hipError_t launch_probe(const DevTable &t, const uint64_t *keys, const uint16_t 
     if (d_n) {  // device-sized batches: the wide-key / large-leaf kernels only
         if (!(t.key_words > 1 || (t.key_width != 0 && t.cap > 128))) return hipErrorInvalidValue;
     }
-    const uint64_t chunks = (n + 63) / 64;
-    const int blocks = grid_for(chunks, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
+    const int mb = max_blocks(tune);
+    const int blocks = grid_for((n + 63) / 64, 4, mb);
     const bool var = t.key_width == 0;
     // wide fixed-width keys, and 8-byte keys in leaves above 128 slots (small rows): leaves of
     // up to 1024 slots -- probe_lane_kernel for leaves of up to 256 slots, probe_split_kernel
-    // above (in 16-probe wave chunks when 64-probe ones cannot fill the chip).  Retired (DESIGN
-    // §4): probe_kernel's one-probe-in-flight form and the split kernel for every leaf size.
+    // above (in 16-probe wave chunks when 64-probe ones cannot fill the chip).  probe_kernel
+    // serves neither.
     if (t.key_words > 1 || (!var && t.cap > 128)) {
         // launch shape from the expected size (a device-sized batch's hint), the grid from n
         const uint64_t sn = d_n && shape_n ? std::min(shape_n, n) : n;
@@ -1972,63 +1991,43 @@ hipError_t launch_probe(const DevTable &t, const uint64_t *keys, const uint16_t 
         // tiny batches (fewer 16-probe chunks than a quarter of that, e.g. CH-Q2's ~2.5 K item
         // lookups): 4-probe wave chunks, a quarter of the serial probes per wave
         const bool tiny = (sn + 15) / 16 < (uint64_t)kSmallBelow / 4;
-        const int mb = tune.max_blocks > 0 ? tune.max_blocks : 16384;
-        const int wblocks = tiny ? grid_for((sn + 3) / 4, 4, mb) : small ? grid_for((sn + 15) / 16, 4, mb) : blocks;
-        // the lane kernel strides over the batch: its grid from the expected size too
-        const int lblocks = grid_for((sn + 63) / 64, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
-#define STAGE_PROBE_W(S, KW)                                                                                  \
-    if (S <= 4)                                                                                               \
-        probe_lane_kernel<(S <= 4 ? S : 4), KW><<<lblocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n); \
-    else if (tiny)                                                                                            \
-        probe_split_kernel<S, KW, 4><<<wblocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n);       \
-    else if (small)                                                                                           \
-        probe_split_kernel<S, KW, 16><<<wblocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n);      \
-    else                                                                                                      \
-        probe_split_kernel<S, KW, 64><<<blocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n)
-#define STAGE_PROBE_WK(KW)                      \
-    switch (t.cap / 64) {                       \
-        case 1: STAGE_PROBE_W(1, KW); break;    \
-        case 2: STAGE_PROBE_W(2, KW); break;    \
-        case 4: STAGE_PROBE_W(4, KW); break;    \
-        case 8: STAGE_PROBE_W(8, KW); break;    \
-        default: STAGE_PROBE_W(16, KW); break;  \
-    }
-        if (t.key_words == 1) {
-            STAGE_PROBE_WK(1)
-        } else if (t.key_words == 2) {
-            STAGE_PROBE_WK(2)
-        } else {
-            STAGE_PROBE_WK(4)
-        }
-#undef STAGE_PROBE_WK
-#undef STAGE_PROBE_W
+        with_geometry(t, [&](auto S, auto KW) {
+            if constexpr (S() <= 4) {  // the lane kernel strides over the batch: its grid from the expected size too
+                probe_lane_kernel<S(), KW()><<<grid_for((sn + 63) / 64, 4, mb), 256, 0, s>>>(t, keys, rids, leaf_in, n,
+                                                                                             out, recs, d_n);
+            } else if (tiny) {
+                probe_split_kernel<S(), KW(), 4><<<grid_for((sn + 3) / 4, 4, mb), 256, 0, s>>>(t, keys, rids, leaf_in, n,
+                                                                                               out, recs, d_n);
+            } else if (small) {
+                probe_split_kernel<S(), KW(), 16><<<grid_for((sn + 15) / 16, 4, mb), 256, 0, s>>>(t, keys, rids, leaf_in,
+                                                                                                  n, out, recs, d_n);
+            } else {
+                probe_split_kernel<S(), KW(), 64><<<blocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n);
+            }
+        });
         return hipGetLastError();
     }
-#define STAGE_PROBE(V, S, G) \
-    probe_kernel<V, S, G><<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, recs, nullptr, nullptr)
+    // probe_kernel<VARLEN, SPL, G, POL, ST>: 10 of its 12 instances, the other 2 in launch_probe_fanout
+    auto launch = [&](auto kernel) {
+        kernel<<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, recs, nullptr, nullptr, nullptr);
+    };
     if (tune.status_bytes == 16) {  // opt-in lean status records: the YCSB geometry only
         if (var || t.cap != 64 || tune.group != 8 || tune.store != 1) return hipErrorInvalidValue;
-        probe_kernel<false, 1, 8, 1, 1, 64, 16><<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, recs,
-                                                                       nullptr, nullptr);
+        launch(probe_kernel<false, 1, 8, 1, 16>);
         return hipGetLastError();
     }
     if (t.cap == 64) {
-        if (var) STAGE_PROBE(true, 1, 4);
-        else if (tune.group == 1) STAGE_PROBE(false, 1, 1);
-        else if (tune.group == 2) STAGE_PROBE(false, 1, 2);
-        else if (tune.group == 4) STAGE_PROBE(false, 1, 4);
-        else if (tune.store == 0)
-            probe_kernel<false, 1, 8, 0><<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, recs, nullptr,
-                                                                 nullptr);
-        else if (tune.store == 2)
-            probe_kernel<false, 1, 8, 2><<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, recs, nullptr,
-                                                                 nullptr);
-        else STAGE_PROBE(false, 1, 8);
+        if (var) launch(probe_kernel<true, 1, 4>);
+        else if (tune.group == 1) launch(probe_kernel<false, 1, 1>);
+        else if (tune.group == 2) launch(probe_kernel<false, 1, 2>);
+        else if (tune.group == 4) launch(probe_kernel<false, 1, 4>);
+        else if (tune.store == 0) launch(probe_kernel<false, 1, 8, 0>);
+        else if (tune.store == 2) launch(probe_kernel<false, 1, 8, 2>);
+        else launch(probe_kernel<false, 1, 8>);
     } else {
-        if (var) STAGE_PROBE(true, 2, 4);
-        else STAGE_PROBE(false, 2, 4);
+        if (var) launch(probe_kernel<true, 2, 4>);
+        else launch(probe_kernel<false, 2, 4>);
     }
-#undef STAGE_PROBE
     return hipGetLastError();
 }
 
@@ -2038,25 +2037,12 @@ hipError_t launch_probe_missed(const DevTable &t, const uint64_t *keys, uint64_t
     if (!probe_missed_supported(t)) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const uint64_t sn = d_n && shape_n ? std::min(shape_n, n) : n;
-    const int blocks = grid_for((sn + 63) / 64, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
-#define STAGE_PROBE_M(S, KW)                                                                                    \
-    probe_lane_kernel<S, KW, true><<<blocks, 256, 0, s>>>(t, keys, nullptr, nullptr, n, out, nullptr, d_n, mrids, \
-                                                          mnq, missed)
-#define STAGE_PROBE_MK(KW)                   \
-    switch (t.cap / 64) {                    \
-        case 1: STAGE_PROBE_M(1, KW); break; \
-        case 2: STAGE_PROBE_M(2, KW); break; \
-        default: STAGE_PROBE_M(4, KW); break; \
-    }
-    if (t.key_words == 1) {
-        STAGE_PROBE_MK(1)
-    } else if (t.key_words == 2) {
-        STAGE_PROBE_MK(2)
-    } else {
-        STAGE_PROBE_MK(4)
-    }
-#undef STAGE_PROBE_MK
-#undef STAGE_PROBE_M
+    const int blocks = grid_for((sn + 63) / 64, 4, max_blocks(tune));
+    with_geometry(t, [&](auto S, auto KW) {
+        if constexpr (S() <= 4)  // probe_missed_supported: leaves of up to 256 slots
+            probe_lane_kernel<S(), KW(), true><<<blocks, 256, 0, s>>>(t, keys, nullptr, nullptr, n, out, nullptr, d_n,
+                                                                      mrids, mnq, missed);
+    });
     return hipGetLastError();
 }
 
@@ -2073,13 +2059,13 @@ hipError_t launch_probe_fanout(const DevTable &t, const uint64_t *keys, const ui
     if (!probe_fanout_supported(t)) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     if ((!recs && !dest) || (!fan && !flist)) return hipErrorInvalidValue;
-    const int blocks = grid_for((n + 63) / 64, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
+    const int blocks = grid_for((n + 63) / 64, 4, max_blocks(tune));
     if (dest)
-        probe_kernel<false, 1, 4, 1, 1, 64, 32, true, true><<<blocks, 256, 0, s>>>(t, keys, nullptr, rids, nullptr, n,
-                                                                                   out, recs, fan, flist, dest);
+        probe_kernel<false, 1, 4, 1, 32, true, true><<<blocks, 256, 0, s>>>(t, keys, nullptr, rids, nullptr, n, out,
+                                                                            recs, fan, flist, dest);
     else
-        probe_kernel<false, 1, 8, 1, 1, 64, 32, true><<<blocks, 256, 0, s>>>(t, keys, nullptr, rids, nullptr, n, out,
-                                                                             recs, fan, flist);
+        probe_kernel<false, 1, 8, 1, 32, true><<<blocks, 256, 0, s>>>(t, keys, nullptr, rids, nullptr, n, out, recs,
+                                                                      fan, flist);
     return hipGetLastError();
 }
 
@@ -2253,50 +2239,25 @@ hipError_t launch_ident(const DevTable &t, const stage_probe_out_dev *out, uint6
 hipError_t launch_resident_reader(const DevTable &t, const ReaderRing &g, hipStream_t s) {
     if (t.key_words != 1 || g.waves == 0 || g.slots % (64 * g.waves)) return hipErrorInvalidValue;
     const dim3 grid(g.waves), block(64);
-    if (t.key_width == 0) {
-        if (t.cap == 64) resident_reader_kernel<true, 1><<<grid, block, 0, s>>>(t, g);
-        else if (t.cap == 128) resident_reader_kernel<true, 2><<<grid, block, 0, s>>>(t, g);
-        else return hipErrorInvalidValue;
-    } else {
-        switch (t.cap / 64) {
-            case 1: resident_reader_kernel<false, 1><<<grid, block, 0, s>>>(t, g); break;
-            case 2: resident_reader_kernel<false, 2><<<grid, block, 0, s>>>(t, g); break;
-            case 4: resident_reader_kernel<false, 4><<<grid, block, 0, s>>>(t, g); break;
-            case 8: resident_reader_kernel<false, 8><<<grid, block, 0, s>>>(t, g); break;
-            case 16: resident_reader_kernel<false, 16><<<grid, block, 0, s>>>(t, g); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
+    if (t.key_width == 0 && t.cap > 128) return hipErrorInvalidValue;
+    with_slot_groups(t, [&](auto S) {
+        if (t.key_width != 0) resident_reader_kernel<false, S()><<<grid, block, 0, s>>>(t, g);
+        else if constexpr (S() <= 2) resident_reader_kernel<true, S()><<<grid, block, 0, s>>>(t, g);
+    });
     return hipGetLastError();
 }
 
 template <int KW, bool VIS, int R = 4>
 static void launch_scan_w(const DevTable &t, const uint64_t *keys, uint64_t n, uint32_t scan_size, uint32_t *counts,
                           uint8_t *recs, const uint32_t *rids, uint8_t *st, hipStream_t s, int blocks) {
-    if (scan_size <= 63) {  // at most 64 kept records per leaf visit: group-skipping LDS form
-#define STAGE_SCAN_C(S)                                                                                        \
-    scan_kernel_compact<false, S, KW, VIS><<<blocks, 256, 0, s>>>(t, keys, nullptr, n, scan_size, counts, recs, \
-                                                                  rids, st)
-        switch (t.cap / 64) {
-            case 1: STAGE_SCAN_C(1); break;
-            case 2: STAGE_SCAN_C(2); break;
-            case 4: STAGE_SCAN_C(4); break;
-            case 8: STAGE_SCAN_C(8); break;
-            default: STAGE_SCAN_C(16);
-        }
-#undef STAGE_SCAN_C
-        return;
-    }
-#define STAGE_SCAN_W(S) \
-    scan_kernel<false, S, R, KW, VIS><<<blocks, 256, 0, s>>>(t, keys, nullptr, n, scan_size, counts, recs, rids, st)
-    switch (t.cap / 64) {
-        case 1: STAGE_SCAN_W(1); break;
-        case 2: STAGE_SCAN_W(2); break;
-        case 4: STAGE_SCAN_W(4); break;
-        case 8: STAGE_SCAN_W(8); break;
-        default: STAGE_SCAN_W(16);
-    }
-#undef STAGE_SCAN_W
+    with_slot_groups(t, [&](auto S) {
+        if (scan_size <= 63)  // at most 64 kept records per leaf visit: group-skipping LDS form
+            scan_kernel_compact<false, S(), KW, VIS><<<blocks, 256, 0, s>>>(t, keys, nullptr, n, scan_size, counts,
+                                                                            recs, rids, st);
+        else
+            scan_kernel<false, S(), R, KW, VIS><<<blocks, 256, 0, s>>>(t, keys, nullptr, n, scan_size, counts, recs,
+                                                                       rids, st);
+    });
 }
 
 template <int R, bool VIS>
@@ -2307,23 +2268,23 @@ static void launch_scan_r(const DevTable &t, const uint64_t *keys, const uint16_
     if (t.key_words == 2) return launch_scan_w<2, VIS>(t, keys, n, scan_size, counts, recs, rids, st, s, blocks);
     if (t.key_words == 4) return launch_scan_w<4, VIS>(t, keys, n, scan_size, counts, recs, rids, st, s, blocks);
     if (!var && t.cap > 128) return launch_scan_w<1, VIS, R>(t, keys, n, scan_size, counts, recs, rids, st, s, blocks);
-#define STAGE_SCAN(V, S) \
-    scan_kernel<V, S, R, 1, VIS><<<blocks, 256, 0, s>>>(t, keys, lens, n, scan_size, counts, recs, rids, st)
+    auto launch = [&](auto kernel) {
+        kernel<<<blocks, 256, 0, s>>>(t, keys, lens, n, scan_size, counts, recs, rids, st);
+    };
     if (t.cap == 64) {
-        if (var) STAGE_SCAN(true, 1);
-        else STAGE_SCAN(false, 1);
+        if (var) launch(scan_kernel<true, 1, R, 1, VIS>);
+        else launch(scan_kernel<false, 1, R, 1, VIS>);
     } else {
-        if (var) STAGE_SCAN(true, 2);
-        else STAGE_SCAN(false, 2);
+        if (var) launch(scan_kernel<true, 2, R, 1, VIS>);
+        else launch(scan_kernel<false, 2, R, 1, VIS>);
     }
-#undef STAGE_SCAN
 }
 
 hipError_t launch_scan(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n, uint32_t scan_size,
                        uint32_t *counts, uint8_t *recs, hipStream_t s, const ScanTuning &tune, const uint32_t *rids,
                        uint8_t *row_status) {
     if (n == 0) return hipSuccess;
-    const int blocks = grid_for(n, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
+    const int blocks = grid_for(n, 4, max_blocks(tune));
     if (row_status) {  // IndexScanExecutor range branch: per-record visibility
         launch_scan_r<4, true>(t, keys, lens, n, scan_size, counts, recs, rids, row_status, s, blocks);
     } else {  // 4 rows in flight per wave (2 and 8 measured no faster)
@@ -2336,15 +2297,9 @@ hipError_t launch_scan_pair(const DevTable &t0, const uint64_t *k0, uint32_t sz0
                             const DevTable &t1, const uint64_t *k1, uint32_t sz1, uint32_t *c1, uint8_t *r1,
                             hipStream_t s) {
     if (!scan_pair_supported(t0, sz0, t1, sz1)) return hipErrorInvalidValue;
-#define STAGE_SCAN_P(S) scan_pair_compact_kernel<S><<<2, 64, 0, s>>>(t0, t1, k0, k1, sz0, sz1, c0, c1, r0, r1)
-    switch (t0.cap / 64) {
-        case 1: STAGE_SCAN_P(1); break;
-        case 2: STAGE_SCAN_P(2); break;
-        case 4: STAGE_SCAN_P(4); break;
-        case 8: STAGE_SCAN_P(8); break;
-        default: STAGE_SCAN_P(16);
-    }
-#undef STAGE_SCAN_P
+    with_slot_groups(t0, [&](auto S) {
+        scan_pair_compact_kernel<S()><<<2, 64, 0, s>>>(t0, t1, k0, k1, sz0, sz1, c0, c1, r0, r1);
+    });
     return hipGetLastError();
 }
 
@@ -2360,34 +2315,18 @@ hipError_t launch_scan_first(const DevTable &t, const uint64_t *keys, uint64_t n
                              const ScanTuning &tune) {
     if (n == 0) return hipSuccess;
     if (t.key_width == 0 || scan_size == 0 || scan_size > 63) return hipErrorInvalidValue;
-    const int blocks = grid_for((n + kFirstChunk - 1) / kFirstChunk, 4, tune.max_blocks > 0 ? tune.max_blocks : 16384);
+    const int blocks = grid_for((n + kFirstChunk - 1) / kFirstChunk, 4, max_blocks(tune));
     // scan_first_split_kernel decides the scans whose start leaf's first visit does, then
     // scan_first_rest_kernel runs the general loop for the rest.  Retired variants (measured
     // no faster): a single-scan kernel, NS scans in lockstep, the prefetching
     // "fast" kernel, the lane-parallel "mono" kernel, segmented stage A, a point-probe first
     // pass, the split kernel at 6 / 7 waves per SIMD.
-#define STAGE_FIRST(S, KW)                                                                                  \
-    scan_first_split_kernel<S, KW, 8><<<blocks, 256, 0, s>>>(t, keys, n, scan_size, rids, words, img_out,    \
-                                                             st_out);                                       \
-    scan_first_rest_kernel<S, KW><<<grid_for((n + 63) / 64, 4, 4096), 256, 0, s>>>(t, keys, n, scan_size, rids, \
-                                                                                words, img_out, st_out)
-#define STAGE_FIRST_K(KW)                      \
-    switch (t.cap / 64) {                      \
-        case 1: STAGE_FIRST(1, KW); break;     \
-        case 2: STAGE_FIRST(2, KW); break;     \
-        case 4: STAGE_FIRST(4, KW); break;     \
-        case 8: STAGE_FIRST(8, KW); break;     \
-        default: STAGE_FIRST(16, KW);          \
-    }
-    if (t.key_words == 4) {
-        STAGE_FIRST_K(4)
-    } else if (t.key_words == 2) {
-        STAGE_FIRST_K(2)
-    } else {
-        STAGE_FIRST_K(1)
-    }
-#undef STAGE_FIRST_K
-#undef STAGE_FIRST
+    with_geometry(t, [&](auto S, auto KW) {
+        scan_first_split_kernel<S(), KW(), 8><<<blocks, 256, 0, s>>>(t, keys, n, scan_size, rids, words, img_out,
+                                                                     st_out);
+        scan_first_rest_kernel<S(), KW()><<<grid_for((n + 63) / 64, 4, 4096), 256, 0, s>>>(t, keys, n, scan_size, rids,
+                                                                                          words, img_out, st_out);
+    });
     return hipGetLastError();
 }
 

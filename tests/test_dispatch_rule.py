@@ -25,7 +25,7 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # the write path's kernels enqueued before an epoch's publish (write_path.hip)
 WRITE_CHAIN = ("wp_set_bases", "wp_keys", "wp_heads", "wp_classify", "wp_speculate", "wp_finish_groups", "wp_jump_links",
                "wp_jump_chain", "wp_jump_codes", "wp_flags", "wp_totals", "wp_headers", "wp_write")
-READ_PROBE = "_ZN5stage12probe_kernelILb0ELi1ELi8ELi1ELi1ELi64ELi32ELb0ELb0EEE"  # the C2 / C3 read probe
+READ_PROBE = "_ZN5stage12probe_kernelILb0ELi1ELi8ELi1ELi32ELb0ELb0EEE"  # the C2 / C3 read probe
 VGPR_GRANULE = 8  # gfx950 allocates a wave's VGPRs in blocks of 8: the slot a probe wave frees
 
 
