@@ -369,6 +369,26 @@ int stage_probe_batch(stage_table *t, const uint64_t *d_keys, const uint16_t *d_
 int stage_probe_batch_ex(stage_table *t, const uint64_t *d_keys, const uint16_t *d_lens,
                          const uint32_t *d_read_ids, const uint32_t *d_leaf_ids, const uint8_t *d_for_update,
                          uint64_t n, stage_probe_out *d_out, uint8_t *d_records, void *stream);
+/* stage_probe_batch that delivers, instead of the tuple row, payload bytes
+ *   [payload_off, payload_off + len) of the tuple the row form would have delivered (same
+ *   (off, len) convention as stage_update) -- for a caller that consumes one column, only those
+ *   bytes are read from the heap and written.  d_window: n rows of stage_window_stride(len)
+ *   bytes; bytes past len are zero; a probe that yields no tuple (NOT_FOUND, CHAIN_MISS,
+ *   FAIL_INVALID_TS) gets an all-zero window.  Status records as stage_probe_batch, honouring
+ *   stage_set_output_layout's status_bytes; its row_stride does not apply.
+ *   STAGE_E_ARG: null table, len == 0, payload_off + len > payload_size, or a null d_window /
+ *   d_out / d_keys with n != 0 -- checked before the table's "needs stage_sync" state.
+ *   stage_set_probe_tuning's max_blocks applies; its group and stage_set_probe_store do not
+ *   (keys of <= 8 bytes in 64- / 128-slot leaves: one fused launch with stage_probe_batch's
+ *   default shape and nontemporal stores; wide keys and larger leaves: the status-only probe and
+ *   a gather of the windows, two launches on `stream`).
+ *   Not covered: is_for_update probes (stage_probe_batch_ex), scans, the sharded entry points
+ *   (stage_probe_sharded*) and the single-key readers (stage_reader_*) deliver rows only. */
+uint32_t stage_window_stride(uint32_t len); /* (len + 15) & ~15 */
+int stage_probe_batch_window(stage_table *t, const uint64_t *d_keys, const uint16_t *d_lens,
+                             const uint32_t *d_read_ids, const uint32_t *d_leaf_ids, uint64_t n,
+                             uint32_t payload_off, uint32_t len, stage_probe_out *d_out,
+                             uint8_t *d_window, void *stream);
 int stage_scan_batch(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens,
                      uint64_t n, uint32_t scan_size, uint32_t *d_counts, uint8_t *d_records,
                      void *stream);
@@ -419,6 +439,13 @@ int stage_host_alloc(uint64_t bytes, void **ptr);
 int stage_host_free(void *ptr);
 int stage_probe_host(stage_table *t, const uint64_t *keys, const uint16_t *lens,
                      const uint32_t *read_ids, uint64_t n, stage_probe_out *out, uint8_t *records);
+/* stage_probe_batch_window for host buffers, through stage_probe_host's chunk pipeline: per
+ *   probe stage_window_stride(len) bytes cross PCIe in place of the row.  `window`: n rows of
+ *   stage_window_stride(len) bytes.  Argument errors as stage_probe_batch_window; calls on one
+ *   table are serialised with stage_probe_host. */
+int stage_probe_host_window(stage_table *t, const uint64_t *keys, const uint16_t *lens,
+                            const uint32_t *read_ids, uint64_t n, uint32_t payload_off, uint32_t len,
+                            stage_probe_out *out, uint8_t *window);
 int stage_reader_create(stage_table *t, uint32_t max_batch, uint32_t max_wait_us,
                         stage_reader **out);
 int stage_reader_create_resident(stage_table *t, uint32_t ring_slots, uint32_t waves, uint32_t life_us,

@@ -548,6 +548,27 @@ int stage_probe_batch(stage_table *t, const uint64_t *d_keys, const uint16_t *d_
     return hip_rc(e, "probe kernel");
 }
 
+uint32_t stage_window_stride(uint32_t len) { return (len + 15u) & ~15u; }
+
+int stage_probe_batch_window(stage_table *t, const uint64_t *d_keys, const uint16_t *d_lens, const uint32_t *d_read_ids,
+                             const uint32_t *d_leaf_ids, uint64_t n, uint32_t payload_off, uint32_t len,
+                             stage_probe_out *d_out, uint8_t *d_window, void *stream) {
+    int rc = check_window(t, payload_off, len);
+    if (rc) return rc;
+    if (n && (!d_keys || !d_out || !d_window)) return fail(STAGE_E_ARG, "null device buffer");
+    rc = need_synced(t);
+    if (rc) return rc;
+    if (n == 0) return STAGE_OK;
+    hipError_t e = hipSetDevice(t->dev.device);
+    if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
+    stage::ProbeTuning tune = t->tune;
+    tune.status_bytes = t->status_bytes;
+    e = stage::launch_probe_window(t->dev.view, d_keys, d_lens, d_read_ids, d_leaf_ids, n,
+                                   facts(t).key_pad() + payload_off, len,
+                                   reinterpret_cast<stage::stage_probe_out_dev *>(d_out), d_window, pick(t, stream), tune);
+    return hip_rc(e, "window probe kernel");
+}
+
 int stage_probe_batch_ex(stage_table *t, const uint64_t *d_keys, const uint16_t *d_lens, const uint32_t *d_read_ids,
                          const uint32_t *d_leaf_ids, const uint8_t *d_for_update, uint64_t n, stage_probe_out *d_out,
                          uint8_t *d_records, void *stream) {

@@ -173,6 +173,16 @@ inline int need_synced(stage_table *t) {
     return STAGE_OK;
 }
 
+// the window probes' (payload_off, len) against the table's parameters alone: needs no device
+// image, so it is checked before need_synced
+inline int check_window(stage_table *t, uint32_t payload_off, uint32_t len) {
+    if (!t) return fail(STAGE_E_ARG, "null table");
+    if (len == 0) return fail(STAGE_E_ARG, "window: len must be at least 1");
+    if ((uint64_t)payload_off + len > facts(t).params().payload_size)
+        return fail(STAGE_E_ARG, "window: payload_off + len exceeds the table's payload_size");
+    return STAGE_OK;
+}
+
 // device-written heap rows (stage_update_batch_device) are pulled into the host arena before a
 // host-side path reads payloads (write_path.hip)
 void ensure_host_rows(stage_table *t);

@@ -86,9 +86,13 @@ static HostPipe *get_pipe(stage_table *t) {
 
 namespace {
 
-// one probe of n <= kPipeChunk keys on a lane: H2D inputs, probe, D2H results (all async)
+// one probe of n <= kPipeChunk keys on a lane: H2D inputs, probe, D2H results (all async).
+// win_len != 0 (stage_probe_host_window): `rows` takes windows of stage_window_stride(win_len)
+// bytes (bytes [row_off, row_off + win_len) of each row) in place of rows of `stride` bytes; a
+// window is no larger than a row, so it uses the lane's row buffer.
 hipError_t pipe_chunk(stage_table *t, stage::PipeLane &l, uint64_t stride, uint32_t kw, const uint64_t *keys,
-                      const uint16_t *lens, const uint32_t *rids, uint64_t n, stage_probe_out *out, uint8_t *rows) {
+                      const uint16_t *lens, const uint32_t *rids, uint64_t n, stage_probe_out *out, uint8_t *rows,
+                      uint32_t row_off = 0, uint32_t win_len = 0) {
     using stage::kPipeChunk;
     uint8_t *dk = l.d, *dl = dk + 8ull * kw * kPipeChunk, *dr = dl + 2 * kPipeChunk, *dout = dr + 4 * kPipeChunk,
             *drow = dout + 32 * kPipeChunk;
@@ -100,11 +104,17 @@ hipError_t pipe_chunk(stage_table *t, stage::PipeLane &l, uint64_t stride, uint3
     view.stride = (uint32_t)stride;
     stage::ProbeTuning tune = t->tune;
     tune.status_bytes = t->status_bytes;  // 16: stage_probe_out16 records, packed
-    e = stage::launch_probe(view, (const uint64_t *)dk, lens ? (const uint16_t *)dl : nullptr,
-                            rids ? (const uint32_t *)dr : nullptr, nullptr, n, (stage::stage_probe_out_dev *)dout,
-                            rows ? drow : nullptr, l.s, tune);
+    if (win_len)
+        e = stage::launch_probe_window(view, (const uint64_t *)dk, lens ? (const uint16_t *)dl : nullptr,
+                                       rids ? (const uint32_t *)dr : nullptr, nullptr, n, row_off, win_len,
+                                       (stage::stage_probe_out_dev *)dout, drow, l.s, tune);
+    else
+        e = stage::launch_probe(view, (const uint64_t *)dk, lens ? (const uint16_t *)dl : nullptr,
+                                rids ? (const uint32_t *)dr : nullptr, nullptr, n, (stage::stage_probe_out_dev *)dout,
+                                rows ? drow : nullptr, l.s, tune);
     if (!e) e = hipMemcpyAsync(out, dout, (uint64_t)tune.status_bytes * n, hipMemcpyDeviceToHost, l.s);
-    if (!e && rows) e = hipMemcpyAsync(rows, drow, stride * n, hipMemcpyDeviceToHost, l.s);
+    const uint64_t row_bytes = win_len ? stage_window_stride(win_len) : stride;
+    if (!e && rows) e = hipMemcpyAsync(rows, drow, row_bytes * n, hipMemcpyDeviceToHost, l.s);
     return e;
 }
 
@@ -360,12 +370,10 @@ int stage_host_alloc(uint64_t bytes, void **ptr) {
 
 int stage_host_free(void *ptr) { return hip_rc(hipHostFree(ptr), "hipHostFree"); }
 
-int stage_probe_host(stage_table *t, const uint64_t *keys, const uint16_t *lens, const uint32_t *read_ids, uint64_t n,
-                     stage_probe_out *out, uint8_t *records) {
-    int rc = need_synced(t);
-    if (rc) return rc;
-    if (n && (!keys || !out)) return fail(STAGE_E_ARG, "null host buffer");
-    if (n == 0) return STAGE_OK;
+// the chunk pipeline of stage_probe_host and stage_probe_host_window (win_len != 0: `records`
+// takes windows, see pipe_chunk); one lock serialises both on a table
+static int probe_host_pipe(stage_table *t, const uint64_t *keys, const uint16_t *lens, const uint32_t *read_ids,
+                           uint64_t n, stage_probe_out *out, uint8_t *records, uint32_t row_off, uint32_t win_len) {
     std::lock_guard<std::mutex> lk(t->pipe_mu);
     return guarded([&] {
         stage::hip_check(hipSetDevice(t->dev.device), "hipSetDevice");
@@ -377,14 +385,35 @@ int stage_probe_host(stage_table *t, const uint64_t *keys, const uint16_t *lens,
             const uint64_t b = c * stage::kPipeChunk, m = std::min<uint64_t>(stage::kPipeChunk, n - b);
             // out: n records of the table's status layout (32 or 16 B)
             auto *ob = reinterpret_cast<stage_probe_out *>(reinterpret_cast<uint8_t *>(out) + b * (uint64_t)t->status_bytes);
+            const uint64_t row_bytes = win_len ? stage_window_stride(win_len) : p->stride;
             stage::hip_check(pipe_chunk(t, l, p->stride, p->kw, keys + b * p->kw, lens ? lens + b : nullptr,
                                         read_ids ? read_ids + b : nullptr, m, ob,
-                                        records ? records + b * p->stride : nullptr),
+                                        records ? records + b * row_bytes : nullptr, row_off, win_len),
                              "probe_host chunk");
         }
         for (auto &l : p->lane) stage::hip_check(hipStreamSynchronize(l.s), "pipe drain");
         return STAGE_OK;
     });
+}
+
+int stage_probe_host(stage_table *t, const uint64_t *keys, const uint16_t *lens, const uint32_t *read_ids, uint64_t n,
+                     stage_probe_out *out, uint8_t *records) {
+    int rc = need_synced(t);
+    if (rc) return rc;
+    if (n && (!keys || !out)) return fail(STAGE_E_ARG, "null host buffer");
+    if (n == 0) return STAGE_OK;
+    return probe_host_pipe(t, keys, lens, read_ids, n, out, records, 0, 0);
+}
+
+int stage_probe_host_window(stage_table *t, const uint64_t *keys, const uint16_t *lens, const uint32_t *read_ids,
+                            uint64_t n, uint32_t payload_off, uint32_t len, stage_probe_out *out, uint8_t *window) {
+    int rc = check_window(t, payload_off, len);
+    if (rc) return rc;
+    if (n && (!keys || !out || !window)) return fail(STAGE_E_ARG, "null host buffer");
+    rc = need_synced(t);
+    if (rc) return rc;
+    if (n == 0) return STAGE_OK;
+    return probe_host_pipe(t, keys, lens, read_ids, n, out, window, facts(t).key_pad() + payload_off, len);
 }
 
 int stage_reader_create(stage_table *t, uint32_t max_batch, uint32_t max_wait_us, stage_reader **out) {

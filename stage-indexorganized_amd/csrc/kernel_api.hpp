@@ -36,6 +36,16 @@ hipError_t launch_resolve(const DevTable &t, const uint64_t *keys, const uint16_
 hipError_t launch_probe(const DevTable &t, const uint64_t *keys, const uint16_t *lens, const uint32_t *rids,
                         const uint32_t *leaf_in, uint64_t n, stage_probe_out_dev *out, uint8_t *recs, hipStream_t s,
                         const ProbeTuning &tune, const uint64_t *d_n = nullptr, uint64_t shape_n = 0);
+// launch_probe that delivers, instead of each probe's row, bytes [row_off, row_off + len) of it
+// (row_off = key pad + payload offset; row_off + len within the heap row, else
+// hipErrorInvalidValue): win holds n windows of (len + 15) & ~15 bytes, zero past len and zero
+// for a probe that yields no tuple; the status records are launch_probe's.  probe_kernel's
+// geometries run one fused launch (probe_window_kernel, tune.max_blocks and tune.status_bytes
+// apply, tune.group and tune.store do not); the lane / split geometries run launch_probe without
+// rows and then window_gather_kernel on the same stream (32-B records).
+hipError_t launch_probe_window(const DevTable &t, const uint64_t *keys, const uint16_t *lens, const uint32_t *rids,
+                               const uint32_t *leaf_in, uint64_t n, uint32_t row_off, uint32_t len,
+                               stage_probe_out_dev *out, uint8_t *win, hipStream_t s, const ProbeTuning &tune);
 // launch_probe with no read id (status records only) that also evaluates each hit at the read
 // ids mrids[0..mnq) and sets missed[q] when a probe produces no tuple at read id q (the miss pass
 // of launch_revisit_segments, folded in).  The lane-probe tables only (probe_missed_supported:

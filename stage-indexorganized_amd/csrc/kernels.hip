@@ -511,6 +511,196 @@ __global__ __launch_bounds__(256) void probe_kernel(DevTable t, const uint64_t *
 }
 
 // ----------------------------------------------------------------------------------------
+// column-window probe (stage_probe_batch_window): payload bytes [payload_off, payload_off + len)
+// of the tuple instead of its whole row
+
+// What a window launch carries beside the probe's arguments (wave-uniform).
+struct WindowArgs {
+    uint32_t src;   // first source byte inside the heap row: key pad + payload_off
+    uint32_t len;   // window bytes, >= 1; src + len <= key pad + payload <= hstride
+    uint32_t W;     // 16-B pieces per window: stage_window_stride(len) / 16
+    uint8_t *win;   // n windows of 16 * W bytes
+};
+
+// 16-B piece c of the window of heap row img.  The source byte src + 16 * c is in general not
+// 16-B aligned (key pad 8 + column offset 100 = byte 108), so the piece comes out of the one or
+// two aligned 16-B chunks that hold it: the second is read only when the piece's last byte lies
+// in it, and that byte is below src + len <= hstride, so no load leaves the row's own hstride
+// bytes (the last heap row is not overrun).  The shift is the same for every piece of a launch
+// (src & 15), so it selects between registers with scalar conditions: no indexed register array.
+// Bytes past len are zero.
+__device__ __forceinline__ u32x4 window_piece(const DevTable &t, uint32_t img, const WindowArgs &w, uint32_t c) {
+    const uint32_t s = w.src + 16u * c;           // first source byte of the piece
+    const uint32_t left = w.len - 16u * c;        // window bytes from this piece on (>= 1)
+    const uint32_t nb = left < 16u ? left : 16u;  // bytes of this piece
+    const uint32_t sh = uni32(w.src & 15u);
+    const u32x4 *row = reinterpret_cast<const u32x4 *>(t.heap + (uint64_t)img * t.hstride);
+    const u32x4 lo = row[s >> 4];
+    u32x4 hi = u32x4{0, 0, 0, 0};
+    if (sh + nb > 16u) hi = row[(s >> 4) + 1u];
+    const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t ds = sh >> 2, bs = 8u * (sh & 3u);
+    uint32_t e[5];  // the five words that hold the piece's 16 bytes, from word ds on
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        e[k] = ds == 0 ? d[k] : ds == 1 ? d[k + 1] : ds == 2 ? d[k + 2] : d[k + 3];
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        o[k] = (uint32_t)(((((uint64_t)e[k + 1]) << 32) | e[k]) >> bs);
+        const uint32_t have = nb > 4u * k ? nb - 4u * k : 0u;  // window bytes in output word k
+        o[k] &= have >= 4u ? ~0u : ((1u << (8u * have)) - 1u);
+    }
+    return u32x4{o[0], o[1], o[2], o[3]};
+}
+
+// The windows of one wave's chunk of cnt <= 64 probes, lane j holding probe base + j's heap row
+// (0xFFFFFFFF: the probe yields no tuple, its window is zero) -- the shape store_chunk receives.
+// The chunk's cnt * W output pieces are consecutive in memory, so they are stored wave-wide and
+// coalesced whatever W is: piece q = 64 * k + lane belongs to probe q / W, piece q % W, and takes
+// that probe's heap row from its lane (ds_bpermute; every lane of the wave is active here).  A
+// probe's pieces may straddle two iterations (W = 7).  U pieces per lane are in flight together.
+// Called by every lane of the wave.
+template <int U = 4>
+__device__ __forceinline__ void store_windows(const DevTable &t, uint32_t lane, uint64_t base, int cnt, uint32_t image,
+                                              const WindowArgs &w) {
+    const uint32_t total = (uint32_t)cnt * w.W;
+    uint8_t *wb = w.win + base * (16ull * w.W);
+    for (uint32_t q0 = 0; q0 < total; q0 += 64u * U) {
+        u32x4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t q = q0 + 64u * u + lane;
+            const uint32_t p = q / w.W, c = q - p * w.W;
+            const uint32_t img = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((p & 63u) << 2), (int)image);
+            v[u] = u32x4{0, 0, 0, 0};
+            if (q < total && img != 0xFFFFFFFFu) v[u] = window_piece(t, img, w, c);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t q = q0 + 64u * u + lane;
+            if (q < total) st16<1>(v[u], wb, q * 16u);
+        }
+    }
+}
+
+// probe_kernel's probe (phases 1-3, G probes in flight per wave) with the window writer in place
+// of the row copy: one launch, the geometries probe_kernel serves (keys of <= 8 bytes, leaves of
+// 64 / 128 slots).  ST: status record bytes, as probe_kernel.  A kernel of its own: probe_kernel's
+// instances stay the measured ones, and nothing here is tuned by stage_set_probe_tuning's group
+// or by the store policy (nontemporal stores throughout).
+template <bool VARLEN, int SPL, int G, int ST>
+__global__ __launch_bounds__(256) void probe_window_kernel(DevTable t, const uint64_t *__restrict__ keys,
+                                                           const uint16_t *__restrict__ lens,
+                                                           const uint32_t *__restrict__ rids,
+                                                           const uint32_t *__restrict__ leaf_in, uint64_t n,
+                                                           stage_probe_out_dev *__restrict__ out, WindowArgs w) {
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        const bool valid = i < n;
+        u32x4 my_a = u32x4{0, 0, 0, 0}, my_b = u32x4{0, 0, 0, 0};  // this lane's probe result
+        uint32_t my_img = 0xFFFFFFFFu;
+        const uint32_t len = t.key_width ? t.key_width : (lens && valid ? (uint32_t)lens[i] : 8u);
+        const uint32_t rid = rids ? (valid ? rids[i] : 0u) : 0xFFFFFFFEu;
+        uint64_t ok;
+        load_okey<1>(keys, i, valid, len, &ok);
+        uint32_t leaf = 0;
+        if (valid) leaf = leaf_in ? leaf_in[i] : resolve_leaf<VARLEN, 1>(t, &ok, len, true);
+        if (leaf > t.nseps) leaf = t.nseps;  // host-supplied ids are clamped to the table
+        const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
+        for (int j0 = 0; j0 < cnt; j0 += G) {
+            uint32_t lf[G], rd[G], xl[G];
+            uint64_t x[G];
+            uint32_t fpb[G][SPL];
+            // phase 1: the fingerprint bytes of G probes' leaf heads
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int j = j0 + g < cnt ? j0 + g : cnt - 1;
+                lf[g] = rl32(leaf, j);
+                rd[g] = rl32(rid, j);
+                x[g] = rl64(ok, j);
+                xl[g] = VARLEN ? rl32(len, j) : t.key_width;
+                const uint8_t *h = t.head + (uint64_t)lf[g] * t.head_bytes;
+#pragma unroll
+                for (int s = 0; s < SPL; ++s) fpb[g][s] = h[s * 64 + lane];
+            }
+            // phase 2: fingerprint candidates read their slot words
+            SlotWords sw[G][SPL];
+            bool cand[G][SPL];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const uint32_t fx = key_fp_words(&x[g], 1);
+#pragma unroll
+                for (int s = 0; s < SPL; ++s) {
+                    cand[g][s] = fpb[g][s] == fx;
+                    sw[g][s] = SlotWords{0, 0, 0, 0};
+                    if (cand[g][s]) sw[g][s] = slot_words(t.slot + (uint64_t)lf[g] * t.cap + s * 64 + lane);
+                }
+            }
+            // phase 3: confirm (order key, key length), first hit in slot order, visibility
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                int slot = -1;
+                uint64_t m = 0;
+                uint32_t nx = 0, im = 0;
+#pragma unroll
+                for (int s = SPL - 1; s >= 0; --s) {
+                    const bool hitl =
+                        cand[g][s] && sw[g][s].okey == x[g] && (!VARLEN || meta_keylen(sw[g][s].meta) == xl[g]);
+                    const uint64_t hit = ballot(hitl);
+                    if (hit) {
+                        const int b = __builtin_ctzll(hit);
+                        slot = s * 64 + b;
+                        m = rl64(sw[g][s].meta, b);
+                        nx = rl32(sw[g][s].next, b);
+                        im = rl32(sw[g][s].image, b);
+                    }
+                }
+                ProbeRes r;
+                visibility(t, slot, m, nx, im, rd[g], r);
+                u32x4 a, b;
+                pack_out(lf[g], r, a, b);
+                if (lane == (uint32_t)(j0 + g)) {
+                    my_a = a;
+                    my_b = b;
+                    my_img = r.image;
+                }
+            }
+        }
+        // phase 4: the chunk's windows, then one coalesced store of its status records
+        store_windows(t, lane, base, cnt, my_img, w);
+        if constexpr (ST == 16) {
+            if (valid)
+                st16<1>(u32x4{my_a.x, my_a.w, my_b.y, my_b.x}, reinterpret_cast<uint8_t *>(out) + base * 16u, lane * 16u);
+        } else {
+            if (valid) {
+                uint8_t *ob = reinterpret_cast<uint8_t *>(out + base);
+                st16<1>(my_a, ob, lane * 32u);
+                st16<1>(my_b, ob, lane * 32u + 16u);
+            }
+        }
+    }
+}
+
+// The windows of probes already answered (32-B status records: the heap row is their image
+// word): the second launch of the window probe on the tables probe_lane_kernel /
+// probe_split_kernel serve.  A wave per 64 probes.
+__global__ __launch_bounds__(256) void window_gather_kernel(DevTable t, const stage_probe_out_dev *__restrict__ out,
+                                                            uint64_t n, WindowArgs w) {
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t base = wave * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        const uint32_t image = i < n ? out[i].w[6] : 0xFFFFFFFFu;
+        store_windows(t, lane, base, (int)((n - base) < 64 ? (n - base) : 64), image, w);
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // resident single-key reader: one-wave workgroups poll a request ring in pinned host memory
 // (the stage_reader_* adapter of BTree::Read callers, b_tree.cpp:2066-2129, without a launch
 // per request).  Ticket q belongs to wave w = q % W as its k-th ticket, k = q / W, and lives in
@@ -2029,6 +2219,48 @@ hipError_t launch_probe(const DevTable &t, const uint64_t *keys, const uint16_t 
         else launch(probe_kernel<false, 2, 4>);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_probe_window(const DevTable &t, const uint64_t *keys, const uint16_t *lens, const uint32_t *rids,
+                               const uint32_t *leaf_in, uint64_t n, uint32_t row_off, uint32_t len,
+                               stage_probe_out_dev *out, uint8_t *win, hipStream_t s, const ProbeTuning &tune) {
+    // the window lies inside a heap row (window_piece's loads rest on it)
+    if (len == 0 || (uint64_t)row_off + len > t.hstride || (n && !win)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const WindowArgs w{row_off, len, (len + 15u) >> 4, win};
+    const int mb = max_blocks(tune);
+    const int blocks = grid_for((n + 63) / 64, 4, mb);
+    const bool var = t.key_width == 0;
+    if (t.key_words > 1 || (!var && t.cap > 128)) {
+        // probe_lane_kernel / probe_split_kernel tables: status records only, then the windows
+        // from their image words, both on the caller's stream
+        ProbeTuning full = tune;
+        full.status_bytes = 32;
+        const hipError_t e = launch_probe(t, keys, lens, rids, leaf_in, n, out, nullptr, s, full);
+        if (e != hipSuccess) return e;
+        window_gather_kernel<<<blocks, 256, 0, s>>>(t, out, n, w);
+        return hipGetLastError();
+    }
+    if (tune.status_bytes == 16 && (var || t.cap != 64)) return hipErrorInvalidValue;  // as launch_probe
+    hipError_t e = hipErrorInvalidValue;  // a leaf size probe_kernel does not serve either
+    with_slot_groups(t, [&](auto S) {
+        if constexpr (S() <= 2) {
+            auto launch = [&](auto kernel) {
+                kernel<<<blocks, 256, 0, s>>>(t, keys, lens, rids, leaf_in, n, out, w);
+                e = hipGetLastError();
+            };
+            // probes in flight per wave: probe_kernel's default shapes
+            if (var) {
+                launch(probe_window_kernel<true, S(), 4, 32>);
+            } else if constexpr (S() == 1) {
+                if (tune.status_bytes == 16) launch(probe_window_kernel<false, 1, 8, 16>);
+                else launch(probe_window_kernel<false, 1, 8, 32>);
+            } else {
+                launch(probe_window_kernel<false, 2, 4, 32>);
+            }
+        }
+    });
+    return e;
 }
 
 hipError_t launch_probe_missed(const DevTable &t, const uint64_t *keys, uint64_t n, stage_probe_out_dev *out,

@@ -112,6 +112,11 @@ SIGNATURES = {
     "stage_traverse_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, c_vp]),
     "stage_export_leaves": (ctypes.c_int64, [c_vp, ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp]),
     "stage_probe_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp]),
+    "stage_window_stride": (ctypes.c_uint32, [ctypes.c_uint32]),
+    "stage_probe_batch_window": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "stage_probe_host_window": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32,
+                                               ctypes.c_uint32, c_vp, c_vp]),
     "stage_probe_batch_ex": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp]),
     "stage_reader_read_ex": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_int,
                                             c_vp, c_vp, c_vp]),

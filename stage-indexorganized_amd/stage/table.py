@@ -110,6 +110,11 @@ def pinned_empty(shape, dtype):
     return np.frombuffer(buf, dtype=dtype, count=count).reshape(shape)
 
 
+def window_stride(length):
+    """stage_window_stride: bytes per probe of a window probe's output, (length + 15) & ~15."""
+    return int(lib().stage_window_stride(int(length)))
+
+
 class Stream:
     def __init__(self):
         p = c_vp()
@@ -468,9 +473,23 @@ class Table:
         check(lib().stage_probe_batch(self.h, d_keys, d_lens, d_read_ids, d_leaf_ids, n, d_out, d_records,
                                       stream), "stage_probe_batch")
 
-    def probe(self, keys, read_ids=None, lens=None, leaf_ids=None, records=True, for_update=None):
+    def probe_device_window(self, d_keys, n, window, d_out, d_window, d_read_ids=None, d_lens=None, d_leaf_ids=None,
+                            stream=None):
+        """stage_probe_batch_window on device pointers: window = (payload_off, len), d_window takes
+        n rows of window_stride(len) bytes."""
+        off, ln = window
+        check(lib().stage_probe_batch_window(self.h, d_keys, d_lens, d_read_ids, d_leaf_ids, n, off, ln, d_out,
+                                             d_window, stream), "stage_probe_batch_window")
+
+    def probe(self, keys, read_ids=None, lens=None, leaf_ids=None, records=True, for_update=None, window=None):
         """Batched BTree::Read + visibility.  Returns (out[n] PROBE_OUT_DTYPE, rows[n, stride] or None).
-        for_update: per-probe is_for_update flags (stage_probe_batch_ex)."""
+        for_update: per-probe is_for_update flags (stage_probe_batch_ex).
+        window=(payload_off, len): (out, win[n, window_stride(len)]) -- the payload bytes
+        [payload_off, payload_off + len) of each tuple instead of its row (stage_probe_batch_window)."""
+        if window is not None:
+            if for_update is not None:
+                raise ValueError("window probes have no is_for_update form")
+            return self._probe_window(keys, read_ids, lens, leaf_ids, window)
         words, n = self.key_buffer(keys)
         bufs = [DeviceBuffer.from_numpy(words) if n else DeviceBuffer(8)]
         d_rids = d_lens = d_leaf = None
@@ -499,6 +518,20 @@ class Table:
         out = d_out.to_numpy(dt, n)
         rows = d_rec.to_numpy(np.uint8, n * self.stride).reshape(n, self.stride) if d_rec else None
         return out, rows
+
+    def _probe_window(self, keys, read_ids, lens, leaf_ids, window):
+        words, n = self.key_buffer(keys)
+        ws = window_stride(window[1])
+        d_keys = DeviceBuffer.from_numpy(words) if n else DeviceBuffer(8)
+        opt = [None if a is None else DeviceBuffer.from_numpy(np.ascontiguousarray(a, t))
+               for a, t in ((read_ids, np.uint32), (lens, np.uint16), (leaf_ids, np.uint32))]
+        d_rids, d_lens, d_leaf = [b.ptr if b else None for b in opt]
+        dt = PROBE_OUT16_DTYPE if getattr(self, "status_bytes", 32) == 16 else PROBE_OUT_DTYPE
+        d_out = DeviceBuffer(n * dt.itemsize)
+        d_win = DeviceBuffer(n * ws)
+        self.probe_device_window(d_keys.ptr, n, window, d_out.ptr, d_win.ptr, d_rids, d_lens, d_leaf)
+        check(lib().stage_device_sync(), "sync")
+        return d_out.to_numpy(dt, n), d_win.to_numpy(np.uint8, n * ws).reshape(n, ws)
 
     def identify(self, keys, read_ids=None):
         """stage_probe_batch + stage_probe_identify: (out[n], ident[n] IDENT_DTYPE) -- each hit's
@@ -557,10 +590,12 @@ class Table:
         check(lib().stage_set_output_layout(self.h, row_stride, status_bytes), "set_output_layout")
         self.status_bytes = status_bytes
 
-    def probe_host(self, keys, read_ids=None, lens=None, records=True, out=None, rows=None):
+    def probe_host(self, keys, read_ids=None, lens=None, records=True, out=None, rows=None, window=None):
         """stage_probe_host: the same probe with host-memory inputs and outputs (pipelined).
         `out` / `rows`: caller-owned result arrays (e.g. pinned_empty) to fill instead of new ones;
-        status records are 16 B after set_output_layout(.., 16)."""
+        status records are 16 B after set_output_layout(.., 16).
+        window=(payload_off, len): stage_probe_host_window -- (out, win[n, window_stride(len)]);
+        `rows` is then the caller-owned window array."""
         keys, n = self.key_buffer(keys)
         rids = None if read_ids is None else np.ascontiguousarray(read_ids, np.uint32)
         ln = None if lens is None else np.ascontiguousarray(lens, np.uint16)
@@ -568,6 +603,14 @@ class Table:
         if out is None:
             out = np.zeros(n, dt)
         assert out.dtype == dt and out.size >= n, "out: n status records of the table's layout"
+        if window is not None:
+            ws = window_stride(window[1])
+            if rows is None:
+                rows = np.zeros((n, ws), np.uint8)
+            assert rows.shape[0] >= n and rows.shape[1] == ws and rows.flags.c_contiguous
+            check(lib().stage_probe_host_window(self.h, keys.ctypes.data, _ptr(ln), _ptr(rids), n, window[0], window[1],
+                                                out.ctypes.data, rows.ctypes.data), "probe_host_window")
+            return out, rows
         if rows is None and records:
             rows = np.zeros((n, self.stride), np.uint8)
         assert rows is None or (rows.shape[0] >= n and rows.shape[1] == self.stride and rows.flags.c_contiguous)
