@@ -382,8 +382,11 @@ int stage_probe_batch_ex(stage_table *t, const uint64_t *d_keys, const uint16_t 
  *   (keys of <= 8 bytes in 64- / 128-slot leaves: one fused launch with stage_probe_batch's
  *   default shape and nontemporal stores; wide keys and larger leaves: the status-only probe and
  *   a gather of the windows, two launches on `stream`).
- *   Not covered: is_for_update probes (stage_probe_batch_ex), scans, the sharded entry points
- *   (stage_probe_sharded*) and the single-key readers (stage_reader_*) deliver rows only. */
+ *   Not covered: is_for_update probes (stage_probe_batch_ex), the sharded entry points
+ *   (stage_probe_sharded*), the single-key readers (stage_reader_*), the first-tuple scan
+ *   (stage_index_scan_first_batch), stock-level and CH-Q2 deliver rows (or their own results)
+ *   only.  Scans have window forms below: stage_scan_batch_window and
+ *   stage_index_scan_batch_window. */
 uint32_t stage_window_stride(uint32_t len); /* (len + 15) & ~15 */
 int stage_probe_batch_window(stage_table *t, const uint64_t *d_keys, const uint16_t *d_lens,
                              const uint32_t *d_read_ids, const uint32_t *d_leaf_ids, uint64_t n,
@@ -403,6 +406,34 @@ int stage_index_scan_batch(stage_table *t, const uint64_t *d_start_keys, const u
                            const uint32_t *d_read_ids, uint64_t n, uint32_t scan_size,
                            uint32_t *d_counts, uint8_t *d_records, uint8_t *d_row_status,
                            void *stream);
+/* stage_scan_batch / stage_index_scan_batch that deliver, instead of each scanned record's row,
+ *   payload bytes [payload_off, payload_off + len) of it (the window convention of
+ *   stage_probe_batch_window) -- for a caller that consumes one column of the records it scans
+ *   (TPC-C stock-level reads 4 bytes of each ORDER_LINE record), only those bytes are read from
+ *   the heap and written.  Defined against the row form of the same scan on the same image:
+ *   d_counts and d_row_status are byte-identical to the row form's;
+ *   d_window[(i*scan_size + j) * stage_window_stride(len) ..] holds row bytes
+ *   [key_pad + payload_off, key_pad + payload_off + len) of the row the row form writes at
+ *   d_records[i*scan_size + j] (key_pad = the key width rounded up to 8), zero past len up to the
+ *   stride; an index-scan record with STAGE_ST_NOT_FOUND gets an all-zero window; positions
+ *   j >= d_counts[i] are not written.  d_window is 16-B aligned (any stage_dev_alloc address).
+ *   d_row_keys (optional, NULL skips it; 8-B aligned): d_row_keys[(i*scan_size + j) * key_pad ..]
+ *   holds the first key_pad bytes of that same row -- the key the scan found, which the window no
+ *   longer carries; zero where the row is zero.
+ *   STAGE_E_ARG: null table, len == 0, payload_off + len > payload_size, or, with n != 0 and
+ *   scan_size != 0, a null d_start_keys / d_counts / d_window (index form: / d_row_status) --
+ *   checked before the table's "needs stage_sync" state.  n == 0 or scan_size == 0 is a
+ *   successful no-op on a synced table (scan_size == 0 zeroes a non-null d_counts, as the row
+ *   form does).  Every table geometry the row forms serve; stage_set_scan_tuning applies.
+ *   Not covered: a host-buffer scan form (none exists for rows either). */
+int stage_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens,
+                            uint64_t n, uint32_t scan_size, uint32_t payload_off, uint32_t len,
+                            uint32_t *d_counts, uint8_t *d_window, uint8_t *d_row_keys, void *stream);
+int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens,
+                                  const uint32_t *d_read_ids, uint64_t n, uint32_t scan_size,
+                                  uint32_t payload_off, uint32_t len, uint32_t *d_counts,
+                                  uint8_t *d_window, uint8_t *d_row_keys, uint8_t *d_row_status,
+                                  void *stream);
 /* The IndexScanExecutor range branch of stage_index_scan_batch consumed only up to its first
  * produced tuple (LATEST or OLD) whose key begins with the start key's first `prefix_words`
  * 8-byte fields (0..key_words) -- the predicate TPC-C stock-level puts on its ORDER_LINE scans
@@ -464,6 +495,10 @@ int stage_reader_destroy(stage_reader *r);
 /* launch shape of stage_probe_batch: probes in flight per wave (1, 2, 4 or 8) and the grid
  * cap in 256-thread blocks (0 = default).  A tuning knob, not a semantic one. */
 int stage_set_probe_tuning(stage_table *t, int group, int max_blocks);
+/* its scan counterpart: the grid cap in 256-thread blocks (0 = default) of the table's scan
+ * launches -- stage_scan_batch, stage_index_scan_batch, their window forms and the first-tuple
+ * scans; a capped grid strides over the batch.  A tuning knob, not a semantic one. */
+int stage_set_scan_tuning(stage_table *t, int max_blocks);
 
 /* cache policy of stage_probe_batch's output stores (rows + status records), 8-probe launch
  * shape: STAGE_STORE_TEMPORAL, STAGE_STORE_NONTEMPORAL (default) or STAGE_STORE_WRITE_THROUGH

@@ -625,6 +625,40 @@ int stage_index_scan_batch(stage_table *t, const uint64_t *d_start_keys, const u
     return hip_rc(e, "index scan kernel");
 }
 
+// both window scans: d_row_status non-null selects the index-scan form
+static int scan_window(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens, const uint32_t *d_read_ids,
+                       uint64_t n, uint32_t scan_size, uint32_t payload_off, uint32_t len, uint32_t *d_counts,
+                       uint8_t *d_window, uint8_t *d_row_keys, uint8_t *d_row_status, bool index, void *stream) {
+    int rc = check_window(t, payload_off, len);
+    if (rc) return rc;
+    if (n && scan_size && (!d_start_keys || !d_counts || !d_window || (index && !d_row_status)))
+        return fail(STAGE_E_ARG, "null device buffer");
+    rc = need_synced(t);
+    if (rc) return rc;
+    if (n == 0) return STAGE_OK;
+    hipError_t e = hipSetDevice(t->dev.device);
+    if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
+    e = stage::launch_scan_window(t->dev.view, d_start_keys, d_lens, n, scan_size, facts(t).key_pad() + payload_off, len,
+                                  facts(t).key_pad(), d_counts, d_window, d_row_keys, pick(t, stream), t->scan_tune,
+                                  index ? d_read_ids : nullptr, index ? d_row_status : nullptr);
+    return hip_rc(e, index ? "window index scan kernel" : "window scan kernel");
+}
+
+int stage_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens, uint64_t n,
+                            uint32_t scan_size, uint32_t payload_off, uint32_t len, uint32_t *d_counts,
+                            uint8_t *d_window, uint8_t *d_row_keys, void *stream) {
+    return scan_window(t, d_start_keys, d_lens, nullptr, n, scan_size, payload_off, len, d_counts, d_window, d_row_keys,
+                       nullptr, false, stream);
+}
+
+int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, const uint16_t *d_lens,
+                                  const uint32_t *d_read_ids, uint64_t n, uint32_t scan_size, uint32_t payload_off,
+                                  uint32_t len, uint32_t *d_counts, uint8_t *d_window, uint8_t *d_row_keys,
+                                  uint8_t *d_row_status, void *stream) {
+    return scan_window(t, d_start_keys, d_lens, d_read_ids, n, scan_size, payload_off, len, d_counts, d_window,
+                       d_row_keys, d_row_status, true, stream);
+}
+
 int stage_index_scan_first_batch(stage_table *t, const uint64_t *d_start_keys, const uint32_t *d_read_ids,
                                  uint64_t n, uint32_t scan_size, uint32_t prefix_words, uint32_t *d_image,
                                  uint8_t *d_status, void *stream) {
@@ -657,6 +691,12 @@ int stage_set_probe_tuning(stage_table *t, int group, int max_blocks) {
         return fail(STAGE_E_ARG, "bad tuning");
     t->tune.group = group;
     t->tune.max_blocks = max_blocks;
+    return STAGE_OK;
+}
+
+int stage_set_scan_tuning(stage_table *t, int max_blocks) {
+    if (!t || max_blocks < 0) return fail(STAGE_E_ARG, "bad tuning");
+    t->scan_tune.max_blocks = max_blocks;
     return STAGE_OK;
 }
 

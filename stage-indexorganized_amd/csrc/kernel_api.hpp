@@ -85,6 +85,17 @@ struct ScanTuning {
 hipError_t launch_scan(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n, uint32_t scan_size,
                        uint32_t *counts, uint8_t *recs, hipStream_t s, const ScanTuning &tune,
                        const uint32_t *rids = nullptr, uint8_t *row_status = nullptr);
+// launch_scan that delivers, instead of each scanned record's row, bytes [row_off, row_off + len)
+// of it (row_off = key pad + payload offset; row_off + len within the heap row, else
+// hipErrorInvalidValue): win[(i*scan_size + j) * ((len + 15) & ~15)] is record j of scan i, zero
+// past len and all zero where the row form zeroes the row; positions j >= counts[i] are not
+// written.  row_keys (optional): the row's first key_pad bytes at (i*scan_size + j) * key_pad.
+// counts and row_status are launch_scan's; the same geometries, grid rule and tuning.  Kernels of
+// their own (scan_window_kernel, scan_window_kernel_compact): launch_scan's code is untouched.
+hipError_t launch_scan_window(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n,
+                              uint32_t scan_size, uint32_t row_off, uint32_t len, uint32_t key_pad, uint32_t *counts,
+                              uint8_t *win, uint8_t *row_keys, hipStream_t s, const ScanTuning &tune,
+                              const uint32_t *rids = nullptr, uint8_t *row_status = nullptr);
 // two single scans (no read id) of two tables in one launch, the same records as launch_scan of
 // each (n = 1): 8-byte keys, leaves of the same size above 128 slots, 1..63 records each
 // (scan_pair_supported; otherwise hipErrorInvalidValue and nothing is launched)

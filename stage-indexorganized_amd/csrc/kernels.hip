@@ -1956,6 +1956,250 @@ __global__ __launch_bounds__(256) void scan_kernel(DevTable t, const uint64_t *_
 }
 
 // ----------------------------------------------------------------------------------------
+// column-window range scan (stage_scan_batch_window / stage_index_scan_batch_window): per scanned
+// record the payload bytes [payload_off, payload_off + len) instead of its row, and optionally
+// the row's first key_pad bytes (its key).  Kernels of their own: scan_kernel's and
+// scan_kernel_compact's instances stay the measured ones.
+
+// What a window scan launch carries beside the scan's arguments (wave-uniform).
+struct ScanWindowArgs {
+    WindowArgs w;       // w.win: n * scan_size windows, record j of scan i at i * scan_size + j
+    uint8_t *row_keys;  // optional: n * scan_size keys of key_pad bytes
+    uint32_t key_pad;   // key bytes at the head of a heap row (a multiple of 8)
+};
+
+// One leaf visit's e records, output positions pos0 .. pos0 + e - 1, their heap rows in rank
+// order in the wave's LDS list rk (0xFFFFFFFF: the record yields no tuple, window and key are
+// zero).  The e * W window pieces are consecutive in memory: chunks of 64 ranks go through
+// store_windows (a 128-slot leaf emits up to 128 records in one visit).  The keys are written by
+// one lane per rank, 64 * key_pad consecutive bytes, from the head of the heap row -- the bytes
+// the row form copies.  Called by every lane of the wave, after the list's writes are fenced.
+__device__ __forceinline__ void store_scan_windows(const DevTable &t, uint32_t lane, uint64_t pos0, uint32_t e,
+                                                   const uint32_t *rk, const ScanWindowArgs &a) {
+    for (uint32_t r0 = 0; r0 < e; r0 += 64u) {
+        const uint32_t cnt = e - r0 < 64u ? e - r0 : 64u;
+        const uint32_t img = lane < cnt ? rk[r0 + lane] : 0xFFFFFFFFu;
+        store_windows(t, lane, pos0 + r0, (int)cnt, img, a.w);
+        if (a.row_keys && lane < cnt) {
+            const uint64_t *src = reinterpret_cast<const uint64_t *>(t.heap + (uint64_t)img * t.hstride);
+            uint64_t *dst = reinterpret_cast<uint64_t *>(a.row_keys + (pos0 + r0 + lane) * a.key_pad);
+            for (uint32_t k = 0; k < (a.key_pad >> 3); ++k)
+                __builtin_nontemporal_store(img != 0xFFFFFFFFu ? src[k] : 0ull, dst + k);
+        }
+    }
+}
+
+// scan_one_compact's sink of the window scan: the visit's heap rows go to the LDS list by rank
+template <bool VIS>
+struct WindowSink {
+    uint64_t pos0;  // first output position of the scan: i * scan_size
+    uint8_t *row_status;
+    uint32_t rid;
+    uint32_t *rk;  // the wave's LDS list, 64 words
+    ScanWindowArgs a;
+    template <int KW>
+    __device__ __forceinline__ bool emit(const DevTable &t, uint64_t base, bool on, uint32_t mslot, uint32_t kr,
+                                         uint32_t produced, const uint64_t *, uint32_t lane) {
+        if (on) {
+            uint32_t img;
+            if (VIS) {
+                uint8_t st;
+                img = scan_visible(t, t.slot[base + mslot], rid, st);
+                row_status[produced + kr] = st;
+            } else {
+                img = t.slot[base + mslot].image;
+            }
+            rk[kr & 63u] = img;
+        }
+        const uint32_t e = (uint32_t)__builtin_popcountll(ballot(on));
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        store_scan_windows(t, lane, pos0 + produced, e, rk, a);
+        __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
+        return false;
+    }
+};
+
+template <bool VARLEN, int SPL, int KW, bool VIS>
+__global__ __launch_bounds__(256) void scan_window_kernel_compact(DevTable t, const uint64_t *__restrict__ keys,
+                                                                  const uint16_t *__restrict__ lens, uint64_t n,
+                                                                  uint32_t scan_size, uint32_t *__restrict__ counts,
+                                                                  const uint32_t *__restrict__ rids,
+                                                                  uint8_t *__restrict__ row_status, ScanWindowArgs a) {
+    __shared__ uint64_t s_keys[4][64 * KW];
+    __shared__ uint32_t s_len[4][64], s_slot[4][64], s_rank[4][64];
+    const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t i = wave; i < n; i += nwaves) {
+        const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+        uint64_t ok[KW];
+        load_okey<KW>(keys, i, true, len, ok);
+        const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+        WindowSink<VIS> sink{i * (uint64_t)scan_size, VIS ? row_status + i * (uint64_t)scan_size : nullptr,
+                             VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u, s_rank[wv], a};
+        const uint32_t produced =
+            scan_one_compact<VARLEN, SPL, KW>(t, ok, len, leaf, scan_size, lane, sink, s_keys[wv], s_len[wv], s_slot[wv]);
+        if (lane == 0) counts[i] = produced;
+    }
+}
+
+// scan_one with the window writer in place of the row copy: the same collection, ranking and
+// continuation, statement for statement (a device function of its own, so that scan_one's code
+// does not move); the emitting lanes hold (heap row, rank) by slot, the LDS list rk (SPL * 64
+// words, the wave's) turns that into rank order for store_scan_windows.
+template <bool VARLEN, int SPL, int KW, bool VIS>
+__device__ void scan_one_window(const DevTable &t, const uint64_t *x0, uint32_t xl, uint32_t leaf, uint32_t scan_size,
+                                uint64_t pos0, uint32_t *count_out, uint32_t lane, uint32_t rid, uint8_t *row_status,
+                                uint32_t *rk, const ScanWindowArgs &a) {
+    uint32_t remaining = scan_size, produced = 0;
+    bool cont = false;
+    uint64_t x[KW];
+#pragma unroll
+    for (int w = 0; w < KW; ++w) x[w] = x0[w];
+    for (uint32_t guard = 0; guard < scan_size + 2 && remaining > 0; ++guard) {
+        const uint64_t base = (uint64_t)leaf * t.cap;
+        const uint32_t mp =
+            *reinterpret_cast<const uint32_t *>(t.head + (uint64_t)leaf * t.head_bytes + head_info_offset(t.cap, KW)) >> 16;
+        uint64_t col[SPL][KW];
+        uint32_t kl[SPL];
+        uint64_t q[SPL];
+#pragma unroll
+        for (int s = 0; s < SPL; ++s)
+#pragma unroll
+            for (int w = 0; w < KW; ++w) col[s][w] = t.okey[((uint64_t)leaf * KW + w) * t.cap + s * 64 + lane];
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) {
+            const uint64_t vm = head_vis(t, leaf, s);
+            const bool vis = (vm >> lane) & 1;
+            kl[s] = t.key_width;
+            if (VARLEN) kl[s] = vis ? meta_keylen(t.slot[base + s * 64 + lane].meta) : 0u;
+            q[s] = ballot(vis && !key_less<VARLEN, KW>(col[s], kl[s], x, xl));
+        }
+        // slot-order truncation: records are collected until more than to_scan are held
+        const uint32_t to_scan = remaining;
+        uint32_t before = 0, m = 0;
+        bool keep[SPL];
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) {
+            const uint32_t rank = before + count_below(q[s]);
+            keep[s] = ((q[s] >> lane) & 1) && rank <= to_scan;
+            before += (uint32_t)__builtin_popcountll(q[s]);
+        }
+        uint64_t km[SPL];
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) {
+            km[s] = ballot(keep[s]);
+            m += (uint32_t)__builtin_popcountll(km[s]);
+        }
+        if (m == 0) break;
+        // key rank among the kept records: the slot-order position inside the monotone prefix
+        uint32_t kr[SPL];
+        uint32_t top = 0;  // one past the highest kept slot
+#pragma unroll
+        for (int s = 0; s < SPL; ++s)
+            if (km[s]) top = (uint32_t)s * 64u + 64u - (uint32_t)__builtin_clzll(km[s]);
+        const bool mono = top <= mp;
+        {
+            uint32_t pre = 0;
+#pragma unroll
+            for (int s = 0; s < SPL; ++s) {
+                kr[s] = mono ? pre + count_below(km[s]) : 0u;
+                pre += (uint32_t)__builtin_popcountll(km[s]);
+            }
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < SPL; ++s2) {
+            uint64_t mm = mono ? 0ull : km[s2];
+            while (mm) {
+                const int b = __builtin_ctzll(mm);
+                mm &= mm - 1;
+                uint64_t ko[KW];
+#pragma unroll
+                for (int w = 0; w < KW; ++w) ko[w] = rl64(col[s2][w], b);
+                const uint32_t kll = rl32(kl[s2], b);
+#pragma unroll
+                for (int s = 0; s < SPL; ++s) kr[s] += key_less<VARLEN, KW>(ko, kll, col[s], kl[s]) ? 1u : 0u;
+            }
+        }
+        // continuation: if the new batch starts with the last key, the iterator stops
+        if (cont) {
+            bool dup = false;
+#pragma unroll
+            for (int s = 0; s < SPL; ++s) {
+                bool eq = kl[s] == xl;
+#pragma unroll
+                for (int w = 0; w < KW; ++w) eq = eq && col[s][w] == x[w];
+                dup |= keep[s] && kr[s] == 0 && eq;
+            }
+            if (ballot(dup)) break;
+        }
+        const uint32_t e = m < remaining ? m : remaining;
+        // the e smallest kept records: heap rows into the list by rank (kr < e <= SPL * 64)
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) {
+            if (keep[s] && kr[s] < e) {
+                uint32_t img;
+                if (VIS) {
+                    uint8_t st;
+                    img = scan_visible(t, t.slot[base + s * 64 + lane], rid, st);
+                    row_status[produced + kr[s]] = st;
+                } else {
+                    img = t.slot[base + s * 64 + lane].image;
+                }
+                rk[kr[s]] = img;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        store_scan_windows(t, lane, pos0 + produced, e, rk, a);
+        __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
+        produced += e;
+        remaining -= e;
+        if (e < m) break;
+        // last record popped: continue from its key with le_child = false (next_leaf_after)
+        uint32_t lastl = 0;
+#pragma unroll
+        for (int s = 0; s < SPL; ++s) {
+            const uint64_t lm = ballot(keep[s] && kr[s] == m - 1);
+            if (lm) {
+                const int b = __builtin_ctzll(lm);
+#pragma unroll
+                for (int w = 0; w < KW; ++w) x[w] = rl64(col[s][w], b);
+                lastl = rl32(kl[s], b);
+            }
+        }
+        xl = lastl;
+        leaf = uni32(next_leaf_after<VARLEN, KW>(t, leaf, x, xl));
+        cont = true;
+    }
+    if (lane == 0) *count_out = produced;
+}
+
+template <bool VARLEN, int SPL, int KW, bool VIS>
+__global__ __launch_bounds__(256) void scan_window_kernel(DevTable t, const uint64_t *__restrict__ keys,
+                                                          const uint16_t *__restrict__ lens, uint64_t n,
+                                                          uint32_t scan_size, uint32_t *__restrict__ counts,
+                                                          const uint32_t *__restrict__ rids,
+                                                          uint8_t *__restrict__ row_status, ScanWindowArgs a) {
+    __shared__ uint32_t s_rank[4][SPL * 64];
+    const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t i = wave; i < n; i += nwaves) {
+        const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+        uint64_t ok[KW];
+        load_okey<KW>(keys, i, true, len, ok);
+        const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+        scan_one_window<VARLEN, SPL, KW, VIS>(t, ok, len, leaf, scan_size, i * (uint64_t)scan_size, counts + i, lane,
+                                              VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u,
+                                              VIS ? row_status + i * (uint64_t)scan_size : nullptr, s_rank[wv], a);
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // MurmurHash64A (misc/murmur/MurmurHash2.cpp:99-147), lane per key
 
 __device__ __forceinline__ uint64_t murmur64a_dev(const uint8_t *p, uint32_t len, uint64_t seed) {
@@ -2523,6 +2767,48 @@ hipError_t launch_scan(const DevTable &t, const uint64_t *keys, const uint16_t *
         launch_scan_r<4, false>(t, keys, lens, n, scan_size, counts, recs, nullptr, nullptr, s, blocks);
     }
     return hipGetLastError();
+}
+
+// launch_scan's dispatch for the window kernels: the compact form for scans of at most 63 records
+// on wide-key and large-leaf tables, the direct form everywhere else
+template <bool VIS>
+static hipError_t launch_scan_window_v(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n,
+                                       uint32_t scan_size, uint32_t *counts, const uint32_t *rids, uint8_t *st,
+                                       const ScanWindowArgs &a, hipStream_t s, int blocks) {
+    const bool var = t.key_width == 0;
+    hipError_t e = hipErrorInvalidValue;  // variable-length keys in leaves above 128 slots: no scan kernel either
+    with_geometry(t, [&](auto S, auto KW) {
+        auto launch = [&](auto kernel) {
+            kernel<<<blocks, 256, 0, s>>>(t, keys, lens, n, scan_size, counts, rids, st, a);
+            e = hipGetLastError();
+        };
+        if constexpr (KW() > 1 || S() > 2) {
+            if (KW() == 1 && var) return;
+            if (scan_size <= 63) launch(scan_window_kernel_compact<false, S(), KW(), VIS>);
+            else launch(scan_window_kernel<false, S(), KW(), VIS>);
+        } else {
+            if (var) launch(scan_window_kernel<true, S(), 1, VIS>);
+            else launch(scan_window_kernel<false, S(), 1, VIS>);
+        }
+    });
+    return e;
+}
+
+hipError_t launch_scan_window(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n,
+                              uint32_t scan_size, uint32_t row_off, uint32_t len, uint32_t key_pad, uint32_t *counts,
+                              uint8_t *win, uint8_t *row_keys, hipStream_t s, const ScanTuning &tune,
+                              const uint32_t *rids, uint8_t *row_status) {
+    // the window and the key lie inside a heap row (window_piece's and the key writer's loads rest on it)
+    if (len == 0 || (uint64_t)row_off + len > t.hstride || key_pad > t.hstride || (key_pad & 7u))
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    if (scan_size == 0)  // nothing to deliver: the counts are the row form's zeros
+        return counts ? hipMemsetAsync(counts, 0, n * sizeof(uint32_t), s) : hipSuccess;
+    if (!win) return hipErrorInvalidValue;
+    const ScanWindowArgs a{WindowArgs{row_off, len, (len + 15u) >> 4, win}, row_keys, key_pad};
+    const int blocks = grid_for(n, 4, max_blocks(tune));
+    if (row_status) return launch_scan_window_v<true>(t, keys, lens, n, scan_size, counts, rids, row_status, a, s, blocks);
+    return launch_scan_window_v<false>(t, keys, lens, n, scan_size, counts, nullptr, nullptr, a, s, blocks);
 }
 
 hipError_t launch_scan_pair(const DevTable &t0, const uint64_t *k0, uint32_t sz0, uint32_t *c0, uint8_t *r0,

@@ -125,8 +125,13 @@ SIGNATURES = {
     "stage_delete_key_owned": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint16, c_u8p]),
     "stage_set_output_layout": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32]),
     "stage_scan_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "stage_scan_batch_window": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
+    "stage_index_scan_batch_window": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32,
+                                                     ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "stage_resolve_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, c_vp, c_vp]),
     "stage_set_probe_tuning": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
+    "stage_set_scan_tuning": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "stage_set_probe_store": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "stage_murmur64a_batch": (ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                                              ctypes.c_uint64, c_vp, c_vp]),

@@ -621,8 +621,63 @@ class Table:
     def reader(self, max_batch=1024, max_wait_us=50, **resident):
         return Reader(self, max_batch, max_wait_us, **resident)
 
-    def range_scan(self, start_keys, scan_size, lens=None):
-        """TableScanExecutor over RangeScanBySize/Iterator.  Returns (counts[n], rows[n, scan_size, stride])."""
+    @property
+    def key_pad(self):
+        """Key bytes at the head of a row: the key width rounded up to 8 (8 for keys of <= 8 bytes)."""
+        return (self.key_width + 7) & ~7 if self.key_width > 8 else 8
+
+    def scan_device_window(self, d_start_keys, n, scan_size, window, d_counts, d_window, d_row_keys=None,
+                           d_row_status=None, d_read_ids=None, d_lens=None, stream=None):
+        """stage_scan_batch_window (d_row_status None) / stage_index_scan_batch_window on device
+        pointers: window = (payload_off, len), d_window takes n * scan_size rows of
+        window_stride(len) bytes, d_row_keys (optional) n * scan_size keys of key_pad bytes."""
+        off, ln = window
+        if d_row_status is None:
+            check(lib().stage_scan_batch_window(self.h, d_start_keys, d_lens, n, scan_size, off, ln, d_counts,
+                                                d_window, d_row_keys, stream), "stage_scan_batch_window")
+        else:
+            check(lib().stage_index_scan_batch_window(self.h, d_start_keys, d_lens, d_read_ids, n, scan_size, off, ln,
+                                                      d_counts, d_window, d_row_keys, d_row_status, stream),
+                  "stage_index_scan_batch_window")
+
+    def _scan_window(self, start_keys, scan_size, read_ids, lens, window, row_keys, index):
+        keys, n = self.key_buffer(start_keys)
+        # an empty batch first: a bad window or a stale image is the library's error, raised
+        # before any device buffer is sized by the window
+        check(lib().stage_scan_batch_window(self.h, None, None, 0, scan_size, window[0], window[1], None, None, None,
+                                            None), "stage_scan_batch_window")
+        ws, kp = window_stride(window[1]), self.key_pad
+        d_keys = DeviceBuffer.from_numpy(keys) if n else DeviceBuffer(8)
+        d_lens = DeviceBuffer.from_numpy(np.ascontiguousarray(lens, np.uint16)) if lens is not None else None
+        d_rid = DeviceBuffer.from_numpy(np.ascontiguousarray(read_ids, np.uint32)) if read_ids is not None else None
+        d_cnt = DeviceBuffer(n * 4)
+        d_win = DeviceBuffer(max(1, n * scan_size * ws))
+        d_key = DeviceBuffer(max(1, n * scan_size * kp)) if row_keys else None
+        d_st = DeviceBuffer(max(1, n * scan_size)) if index else None
+        for b in (d_win, d_key, d_st):
+            if b is not None:
+                b.memset(0)
+        self.scan_device_window(d_keys.ptr, n, scan_size, window, d_cnt.ptr, d_win.ptr, d_key.ptr if d_key else None,
+                                d_st.ptr if d_st else None, d_rid.ptr if d_rid else None,
+                                d_lens.ptr if d_lens else None)
+        check(lib().stage_device_sync(), "sync")
+        res = [d_cnt.to_numpy(np.uint32, n), d_win.to_numpy(np.uint8, n * scan_size * ws).reshape(n, scan_size, ws)]
+        if row_keys:
+            res.append(d_key.to_numpy(np.uint8, n * scan_size * kp).reshape(n, scan_size, kp))
+        if index:
+            res.append(d_st.to_numpy(np.uint8, n * scan_size).reshape(n, scan_size))
+        return tuple(res)
+
+    def range_scan(self, start_keys, scan_size, lens=None, window=None, row_keys=False):
+        """TableScanExecutor over RangeScanBySize/Iterator.  Returns (counts[n], rows[n, scan_size, stride]).
+        window=(payload_off, len): (counts, win[n, scan_size, window_stride(len)]) -- the payload
+        bytes [payload_off, payload_off + len) of each scanned record instead of its row
+        (stage_scan_batch_window); with row_keys=True also keys[n, scan_size, key_pad], each row's
+        first key_pad bytes."""
+        if window is not None:
+            return self._scan_window(start_keys, scan_size, None, lens, window, row_keys, False)
+        if row_keys:
+            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
         keys, n = self.key_buffer(start_keys)
         d_keys = DeviceBuffer.from_numpy(keys)
         d_lens = DeviceBuffer.from_numpy(np.ascontiguousarray(lens, np.uint16)) if lens is not None else None
@@ -636,8 +691,14 @@ class Table:
         rows = d_rec.to_numpy(np.uint8, n * scan_size * self.stride).reshape(n, scan_size, self.stride)
         return counts, rows
 
-    def index_scan(self, start_keys, scan_size, read_ids=None, lens=None):
-        """IndexScanExecutor range branch: (counts[n], rows[n, scan_size, stride], status[n, scan_size])."""
+    def index_scan(self, start_keys, scan_size, read_ids=None, lens=None, window=None, row_keys=False):
+        """IndexScanExecutor range branch: (counts[n], rows[n, scan_size, stride], status[n, scan_size]).
+        window=(payload_off, len): (counts, win[n, scan_size, window_stride(len)], [keys,] status)
+        as range_scan's window form (stage_index_scan_batch_window)."""
+        if window is not None:
+            return self._scan_window(start_keys, scan_size, read_ids, lens, window, row_keys, True)
+        if row_keys:
+            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
         keys, n = self.key_buffer(start_keys)
         d_keys = DeviceBuffer.from_numpy(keys)
         d_lens = DeviceBuffer.from_numpy(np.ascontiguousarray(lens, np.uint16)) if lens is not None else None
