@@ -434,6 +434,53 @@ int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, 
                                   uint32_t payload_off, uint32_t len, uint32_t *d_counts,
                                   uint8_t *d_window, uint8_t *d_row_keys, uint8_t *d_row_status,
                                   void *stream);
+/* Whole-table scans: every record of the leaves [leaf_begin, leaf_end), rows or one column --
+ *   TableScanExecutor::Execute with scan_sz == -1 (executor.h:573-642: every leaf, every slot in
+ *   slot order, ScanLeafNode), per record IndexScanExecutor's rule when a read id is given
+ *   (executor.h:465-534).  Leaves are numbered in key order, as stage_probe_out.leaf numbers them;
+ *   leaf_end == UINT64_MAX means "through the last leaf".  No start keys, no tree descent, no key
+ *   compare: the scan streams leaf heads, slot words and heap rows.
+ *   read_id is a HOST pointer.  NULL = raw mode, ScanLeafNode: in each leaf the slots
+ *   0 .. record_count-1 in slot order, every slot whose RecordMetadata word is non-zero (a deleted
+ *   slot's word is 0); record k (0-based, over the whole range) is the heap row of the slot's
+ *   current image, [key padded to 8][payload], written at d_records[k * row stride] with
+ *   stage_scan_batch's row stride on this table; no visibility is evaluated, every record is
+ *   STAGE_ST_LATEST.  Non-NULL = snapshot mode at *read_id: the slots the range iterator considers
+ *   (the leaf's visible slots), in the same leaf and slot order -- not KeyCompare order -- each
+ *   evaluated as stage_index_scan_batch evaluates a record: STAGE_ST_LATEST (the leaf image),
+ *   STAGE_ST_OLD (the TupleHeader version with begin <= read_id <= end) or STAGE_ST_NOT_FOUND
+ *   (row, window and key zero); every considered slot takes one output position.
+ *   d_count[0] = the records the range holds, also when that exceeds max_records: only positions
+ *   < max_records are written and nothing past them is touched; max_records == 0 is a count-only
+ *   call (the record buffers may be NULL).  d_leaf_offsets (optional, leaf_end - leaf_begin + 1
+ *   words): d_leaf_offsets[i] = the position of leaf leaf_begin + i's first record, the last entry
+ *   = d_count[0]; leaf i was delivered whole when d_leaf_offsets[i + 1] <= max_records, so a
+ *   caller whose output was truncated resumes at the first leaf that was not (with the cut on a
+ *   leaf boundary: the first leaf whose offset is >= max_records).  d_row_meta (optional): d_row_meta[k] = the slot's RecordMetadata word (key
+ *   length, commit id, control bit).  d_row_status (optional, both modes): the status per record.
+ *   Window form: the same record set, order, count, offsets, meta and status;
+ *   d_window[k * stage_window_stride(len) ..] holds row bytes [key_pad + payload_off, key_pad +
+ *   payload_off + len) of the row the row form writes at position k, zero past len up to the
+ *   stride; d_row_keys (optional): the row's first key_pad bytes at k * key_pad.  Alignment as
+ *   stage_scan_batch_window (d_window 16-B, d_row_keys 8-B; d_records 16-B).
+ *   STAGE_E_ARG, checked before the table's "needs stage_sync" state: null table, leaf_begin >
+ *   leaf_end, null d_count, max_records != 0 with a null d_records / d_window, window form:
+ *   len == 0 or payload_off + len > payload_size.  Then STAGE_E_STATE for a stale image, then
+ *   STAGE_E_ARG for a leaf_end (when not UINT64_MAX) or leaf_begin above the published leaf count.
+ *   An empty range succeeds on a synced table: d_count[0] = 0, d_leaf_offsets[0] = 0.
+ *   Every table geometry the scans serve; stage_set_scan_tuning's grid cap applies.  The leaf
+ *   counts live in the table's per-call scratch until the work enqueued on `stream` ends.
+ *   Not covered: a host-buffer form, predicates or aggregates on the device, sharded forms. */
+int stage_table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                     const uint32_t *read_id,          /* host pointer; NULL = raw */
+                     uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
+                     uint8_t *d_records, uint64_t *d_row_meta, uint8_t *d_row_status,
+                     void *stream);
+int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                            const uint32_t *read_id, uint32_t payload_off, uint32_t len,
+                            uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
+                            uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_meta,
+                            uint8_t *d_row_status, void *stream);
 /* The IndexScanExecutor range branch of stage_index_scan_batch consumed only up to its first
  * produced tuple (LATEST or OLD) whose key begins with the start key's first `prefix_words`
  * 8-byte fields (0..key_words) -- the predicate TPC-C stock-level puts on its ORDER_LINE scans

@@ -659,6 +659,53 @@ int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, 
                        d_row_keys, d_row_status, true, stream);
 }
 
+// both whole-table scans (TableScanExecutor, executor.h:573-642; per record IndexScanExecutor's
+// rule, executor.h:465-534): `window` selects the window form, d_out is d_records / d_window
+static int table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id, bool window,
+                      uint32_t payload_off, uint32_t len, uint64_t max_records, uint64_t *d_count,
+                      uint64_t *d_leaf_offsets, uint8_t *d_out, uint8_t *d_row_keys, uint64_t *d_row_meta,
+                      uint8_t *d_row_status, void *stream) {
+    if (!t) return fail(STAGE_E_ARG, "null table");
+    int rc = window ? check_window(t, payload_off, len) : STAGE_OK;
+    if (rc) return rc;
+    if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
+    if (!d_count) return fail(STAGE_E_ARG, "table scan: null d_count");
+    if (max_records && !d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
+    rc = need_synced(t);
+    if (rc) return rc;
+    const uint64_t nleaves = t->dev.view.nleaves;
+    if (leaf_end == UINT64_MAX) leaf_end = nleaves;
+    if (leaf_end > nleaves || leaf_begin > leaf_end)
+        return fail(STAGE_E_ARG, "table scan: the leaf range exceeds the table's " + std::to_string(nleaves) + " leaves");
+    return guarded([&] {
+        hipError_t e = hipSetDevice(t->dev.device);
+        if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
+        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
+        uint8_t *scratch = nl ? stage::scratch_bytes(t->dev, stage::table_scan_scratch_bytes(nl)) : nullptr;
+        const stage::TableScanOut o{max_records, d_count, d_leaf_offsets, window ? nullptr : d_out,
+                                    window ? d_out : nullptr, window ? d_row_keys : nullptr, d_row_meta, d_row_status};
+        e = stage::launch_table_scan(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr, read_id ? *read_id : 0u,
+                                     window ? facts(t).key_pad() + payload_off : 0u, window ? len : 0u,
+                                     facts(t).key_pad(), o, scratch, pick(t, stream), t->scan_tune);
+        return hip_rc(e, "table scan kernels");
+    });
+}
+
+int stage_table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                     uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_records,
+                     uint64_t *d_row_meta, uint8_t *d_row_status, void *stream) {
+    return table_scan(t, leaf_begin, leaf_end, read_id, false, 0, 0, max_records, d_count, d_leaf_offsets, d_records,
+                      nullptr, d_row_meta, d_row_status, stream);
+}
+
+int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                            uint32_t payload_off, uint32_t len, uint64_t max_records, uint64_t *d_count,
+                            uint64_t *d_leaf_offsets, uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_meta,
+                            uint8_t *d_row_status, void *stream) {
+    return table_scan(t, leaf_begin, leaf_end, read_id, true, payload_off, len, max_records, d_count, d_leaf_offsets,
+                      d_window, d_row_keys, d_row_meta, d_row_status, stream);
+}
+
 int stage_index_scan_first_batch(stage_table *t, const uint64_t *d_start_keys, const uint32_t *d_read_ids,
                                  uint64_t n, uint32_t scan_size, uint32_t prefix_words, uint32_t *d_image,
                                  uint8_t *d_status, void *stream) {

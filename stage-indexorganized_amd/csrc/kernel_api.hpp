@@ -96,6 +96,32 @@ hipError_t launch_scan_window(const DevTable &t, const uint64_t *keys, const uin
                               uint32_t scan_size, uint32_t row_off, uint32_t len, uint32_t key_pad, uint32_t *counts,
                               uint8_t *win, uint8_t *row_keys, hipStream_t s, const ScanTuning &tune,
                               const uint32_t *rids = nullptr, uint8_t *row_status = nullptr);
+// Whole-table scan: every record of leaves [leaf0, leaf0 + nl) in leaf and slot order, record k of
+// the range at output position k.  snapshot false: ScanLeafNode -- the slots below the leaf's
+// record count whose meta word is non-zero, the current image, status ST_LATEST.  snapshot true:
+// the slots of the head's visible masks, each evaluated at read id `rid` like launch_scan's
+// row_status form (ST_NOT_FOUND: row / window / key zero; the slot still takes a position).
+// len == 0: rows of t.stride bytes to o.recs; len != 0: windows [row_off, row_off + len) of
+// (len + 15) & ~15 bytes to o.win and, optionally, the rows' first key_pad bytes to o.row_keys
+// (launch_scan_window's conventions).  o.count[0] = the records of the range; only positions
+// < o.max_records are written (0: count only, no record buffer needed).  o.leaf_offsets
+// (optional, nl + 1 words): the position of each leaf's first record, then the count.
+// scratch: table_scan_scratch_bytes(nl) bytes, 8-B aligned, used until the launches end on s.
+// Three launches, none of which waits for another workgroup; tune's grid cap applies to each.
+struct TableScanOut {
+    uint64_t max_records;
+    uint64_t *count;
+    uint64_t *leaf_offsets;
+    uint8_t *recs;
+    uint8_t *win;
+    uint8_t *row_keys;
+    uint64_t *row_meta;
+    uint8_t *row_status;
+};
+uint64_t table_scan_scratch_bytes(uint64_t nl);
+hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                             uint32_t row_off, uint32_t len, uint32_t key_pad, const TableScanOut &o, uint8_t *scratch,
+                             hipStream_t s, const ScanTuning &tune);
 // two single scans (no read id) of two tables in one launch, the same records as launch_scan of
 // each (n = 1): 8-byte keys, leaves of the same size above 128 slots, 1..63 records each
 // (scan_pair_supported; otherwise hipErrorInvalidValue and nothing is launched)

@@ -129,6 +129,11 @@ SIGNATURES = {
                                                ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp]),
     "stage_index_scan_batch_window": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32,
                                                      ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "stage_table_scan": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp]),
+    "stage_table_scan_window": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp]),
     "stage_resolve_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, c_vp, c_vp]),
     "stage_set_probe_tuning": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
     "stage_set_scan_tuning": (ctypes.c_int, [c_vp, ctypes.c_int]),

@@ -5,6 +5,7 @@ read path: `read`/`probe` = BTree::Read + IndexScanExecutor point lookup (batche
 `range_scan` = RangeScanBySize + Iterator + TableScanExecutor, `insert`/`update`/... = the
 host write path.  Numpy arrays in, numpy arrays out; device buffers are managed here.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -35,6 +36,9 @@ Q2_REC_DTYPE = np.dtype([
 assert Q2_REC_DTYPE.itemsize == 48
 RC_INVALID, RC_OK, RC_KEY_EXISTS, RC_NOT_FOUND = 0, 1, 2, 3
 RC_NOT_NEEDED_UPDATE, RC_DIRTY = 7, 9
+# stage_table_scan: "through the last leaf", and what Table.table_scan returns
+LEAF_END = 0xFFFFFFFFFFFFFFFF
+TableScanResult = collections.namedtuple("TableScanResult", "count offsets records keys meta status")
 
 
 def _ptr(a):
@@ -716,6 +720,60 @@ class Table:
         rows = d_rec.to_numpy(np.uint8, n * scan_size * self.stride).reshape(n, scan_size, self.stride)
         st = d_st.to_numpy(np.uint8, n * scan_size).reshape(n, scan_size)
         return counts, rows, st
+
+    def table_scan_device(self, leaves, read_id, max_records, d_count, d_leaf_offsets=None, d_out=None, window=None,
+                          d_row_keys=None, d_row_meta=None, d_row_status=None, stream=None):
+        """stage_table_scan (window None) / stage_table_scan_window on device buffers (DeviceBuffer
+        or raw pointers): leaves = (begin, end) or None for the whole table, read_id None = raw
+        mode; d_out takes max_records rows of `stride` bytes or windows of window_stride(len)
+        bytes, d_leaf_offsets end - begin + 1 u64 words, d_row_keys key_pad bytes per record,
+        d_row_meta one u64 and d_row_status one byte per record.  Enqueued on `stream`."""
+        def p(b):
+            return getattr(b, "ptr", b)
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        if window is None:
+            check(lib().stage_table_scan(self.h, begin, end, rid, max_records, p(d_count), p(d_leaf_offsets), p(d_out),
+                                         p(d_row_meta), p(d_row_status), p(stream)), "stage_table_scan")
+        else:
+            check(lib().stage_table_scan_window(self.h, begin, end, rid, window[0], window[1], max_records, p(d_count),
+                                                p(d_leaf_offsets), p(d_out), p(d_row_keys), p(d_row_meta),
+                                                p(d_row_status), p(stream)), "stage_table_scan_window")
+
+    def table_scan(self, leaves=None, read_id=None, window=None, row_keys=False, row_meta=False, max_records=None):
+        """TableScanExecutor with scan_sz == -1: every record of the leaves [begin, end) (None: the
+        whole table) in leaf and slot order.  read_id None: ScanLeafNode's records (every slot
+        with a non-zero meta word, the current image); a read id: the visible slots, each
+        evaluated as index_scan evaluates a record.  Returns TableScanResult(count, offsets,
+        records, keys, meta, status): count = the records of the range (also when max_records cuts
+        the output), offsets[i] = the position of leaf begin + i's first record (last = count),
+        records = rows[m, stride] or, with window=(payload_off, len), win[m, window_stride(len)]
+        for the m = min(count, max_records) delivered records, keys[m, key_pad] with
+        row_keys=True (window form), meta[m] with row_meta=True, status[m]."""
+        if row_keys and window is None:
+            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+        d_cnt = DeviceBuffer(8)
+        # count first: a bad range or window, or a stale image, is the library's error, raised
+        # before any buffer is sized
+        self.table_scan_device((begin, end), read_id, 0, d_cnt, window=window)
+        check(lib().stage_device_sync(), "sync")
+        count = int(d_cnt.to_numpy(np.uint64, 1)[0])
+        if end == LEAF_END:
+            end = self.stats()["leaves"]
+        m = count if max_records is None else min(count, int(max_records))
+        width = self.stride if window is None else window_stride(window[1])
+        d_off = DeviceBuffer((end - begin + 1) * 8)
+        d_out = DeviceBuffer(max(1, m * width))
+        d_key = DeviceBuffer(max(1, m * self.key_pad)) if row_keys else None
+        d_meta = DeviceBuffer(max(1, m * 8)) if row_meta else None
+        d_st = DeviceBuffer(max(1, m))
+        self.table_scan_device((begin, end), read_id, m, d_cnt, d_off, d_out, window, d_key, d_meta, d_st)
+        check(lib().stage_device_sync(), "sync")
+        return TableScanResult(int(d_cnt.to_numpy(np.uint64, 1)[0]), d_off.to_numpy(np.uint64, end - begin + 1),
+                               d_out.to_numpy(np.uint8, m * width).reshape(m, width),
+                               d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
+                               d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m))
 
     def index_scan_first(self, start_keys, scan_size, prefix_words, read_ids=None):
         """index_scan consumed up to its first LATEST / OLD tuple carrying the start key's first
