@@ -556,6 +556,15 @@ int stage_set_scan_tuning(stage_table *t, int max_blocks);
 #define STAGE_STORE_WRITE_THROUGH 2
 int stage_set_probe_store(stage_table *t, int policy);
 
+/* form of stage_probe_batch's kernel for fixed-width keys of at most 8 bytes in 64- / 128-slot
+ * leaves: STAGE_PROBE_FORM_WAVE (a wave per probe) or STAGE_PROBE_FORM_LANE (default: the search
+ * a lane per probe, the rows wave-wide; taken at the default group and store policy, every other
+ * table and launch shape keeps the wave form).  Same results, byte for byte.  A tuning knob, not a
+ * semantic one. */
+#define STAGE_PROBE_FORM_WAVE 0
+#define STAGE_PROBE_FORM_LANE 1
+int stage_set_probe_form(stage_table *t, int form);
+
 /* MurmurHash64A (misc/murmur/MurmurHash2.cpp:99-147) over n keys of key_len bytes laid out
  * key_stride bytes apart; d_out[i] = hash.  Used as the multi-GPU shard router. */
 int stage_murmur64a_batch(const void *d_keys, uint32_t key_len, uint32_t key_stride, uint64_t seed,

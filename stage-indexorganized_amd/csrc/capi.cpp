@@ -754,6 +754,13 @@ int stage_set_probe_store(stage_table *t, int policy) {
     return STAGE_OK;
 }
 
+int stage_set_probe_form(stage_table *t, int form) {
+    if (!t || (form != STAGE_PROBE_FORM_WAVE && form != STAGE_PROBE_FORM_LANE))
+        return fail(STAGE_E_ARG, "bad probe form");
+    t->tune.form = form;
+    return STAGE_OK;
+}
+
 int stage_murmur64a_batch(const void *d_keys, uint32_t key_len, uint32_t key_stride, uint64_t seed, uint64_t n,
                           uint64_t *d_out, void *stream) {
     if (n && (!d_keys || !d_out || key_stride < key_len)) return fail(STAGE_E_ARG, "bad arguments");

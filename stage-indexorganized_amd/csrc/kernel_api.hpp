@@ -21,12 +21,18 @@ struct alignas(8) ImageDescDev {
     uint32_t mode;
 };
 
+// the point probe's two forms for fixed-width keys of at most 8 bytes in 64- / 128-slot leaves:
+// probe_kernel (a wave per probe) or probe_rows_kernel (front end a lane per probe, rows wave-wide;
+// taken at group 8 and nontemporal stores only).  Mirrors of STAGE_PROBE_FORM_* (include/stage_hip.h).
+constexpr int kProbeFormWave = 0, kProbeFormLane = 1;
 struct ProbeTuning {
     int group = 8;         // probes per wave in flight (swept: 8 > 4 > 2 > 1 at 100M rows)
     int max_blocks = 0;    // 0 = default grid cap (16384 blocks of 256 threads)
     int store = 1;         // output stores: 0 temporal, 1 nontemporal, 2 write-through (sc1)
     int status_bytes = 32; // status record: 32 (stage_probe_out) or 16 (stage_probe_out16)
+    int form = kProbeFormLane; // stage_set_probe_form (LANE measured faster at every shape)
 };
+constexpr int kProbeRows = 16;  // probe_rows_kernel's rows in flight per wave (swept: 16 > 8)
 
 hipError_t launch_resolve(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t n, int le_child,
                           uint32_t *out, hipStream_t s);

@@ -1632,6 +1632,130 @@ __global__ __launch_bounds__(256) void probe_lane_kernel(DevTable t, const uint6
     }
 }
 
+// Point probes of probe_kernel's fixed-width geometry (keys of at most 8 bytes, leaves of 64 /
+// 128 slots) in its second form (ProbeTuning::form = 1, stage_set_probe_form): the front end a
+// lane per probe as probe_lane_kernel's -- descent, the leaf head's fingerprint bytes as SPL x 4
+// 16-B loads, byte-wise compares in registers, the first three candidates confirmed in rounds
+// that all lanes issue together, then the walk of the rest; visibility() per lane with the
+// latest-version fast path inline -- and no broadcast, ballot or LDS: probe_kernel's phases 1-3
+// are wave-uniform work that 63 of 64 lanes repeat.  The status record and the image
+// index stay in the probe's own lane; invalid lanes (i >= n) issue no load.  The back end is
+// probe_kernel's phase 4 with R rows in flight per wave: image by readlane, the heap row's 16-B
+// chunks, nontemporal stores -- the same bytes as probe_kernel's (a probe without a tuple gets a
+// zero row, row bytes past the heap row are zero, nothing is written when recs is null).
+// A kernel of its own so that probe_kernel's instances stay instruction for instruction as measured.
+template <int SPL, int R, int ST>
+__global__ __launch_bounds__(256) void probe_rows_kernel(DevTable t, const uint64_t *__restrict__ keys,
+                                                         const uint32_t *__restrict__ rids,
+                                                         const uint32_t *__restrict__ leaf_in, uint64_t n,
+                                                         stage_probe_out_dev *__restrict__ out,
+                                                         uint8_t *__restrict__ recs) {
+    static_assert(SPL <= 2, "probe_kernel's leaves: 64 or 128 slots");
+    const uint32_t lane = lane_id();
+    // wave-uniform wave index: the chunk base and the row addresses in SGPRs (as probe_kernel)
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t out_chunks = t.stride >> 4;
+    const uint32_t len = t.key_width;
+    for (uint64_t base = wave * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        const bool valid = i < n;
+        const uint32_t rid = rids ? (valid ? rids[i] : 0u) : 0xFFFFFFFEu;
+        uint64_t ok;
+        load_okey<1>(keys, i, valid, len, &ok);
+        uint32_t leaf = 0;
+        if (valid) leaf = leaf_in ? leaf_in[i] : resolve_leaf<false, 1>(t, &ok, len, true);
+        if (leaf > t.nseps) leaf = t.nseps;  // host-supplied ids are clamped to the table
+        const uint32_t rep = (key_fp_words(&ok, 1) & 0xFFu) * 0x01010101u;
+        // the head: fingerprint byte j = slot j
+        u32x4 hv[SPL * 4];
+        const u32x4 *hp = reinterpret_cast<const u32x4 *>(t.head + (uint64_t)leaf * t.head_bytes);
+#pragma unroll
+        for (int q = 0; q < SPL * 4; ++q) hv[q] = valid ? hp[q] : u32x4{0, 0, 0, 0};
+        // candidates in slot order: the first three kept, the count of all
+        uint32_t c0 = 0, c1 = 0, c2 = 0, nc = 0;
+#pragma unroll
+        for (int q = 0; q < SPL * 4; ++q) {
+            const uint32_t wq[4] = {hv[q].x, hv[q].y, hv[q].z, hv[q].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t w = wq[e] ^ rep;
+                uint32_t zm = ~(((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u;  // bytes equal to the fingerprint
+                while (zm) {
+                    const uint32_t sl = (uint32_t)(q * 16 + e * 4) + ((uint32_t)__builtin_ctz(zm) >> 3);
+                    c0 = nc == 0 ? sl : c0;
+                    c1 = nc == 1 ? sl : c1;
+                    c2 = nc == 2 ? sl : c2;
+                    ++nc;
+                    zm &= zm - 1;
+                }
+            }
+        }
+        if (!valid) nc = 0;
+        int slot = -1;
+        uint64_t m = 0;
+        uint32_t nx = 0, im = 0;
+        const uint64_t lb = (uint64_t)leaf * t.cap;
+        auto confirm = [&](uint32_t sl) { return confirm_slot<1>(t, leaf, lb, sl, &ok, slot, m, nx, im); };
+        // rounds: every lane still looking confirms its next candidate, the loads together
+        if (nc > 0) confirm(c0);
+        if (slot < 0 && nc > 1) confirm(c1);
+        if (slot < 0 && nc > 2) confirm(c2);
+        if (slot < 0 && nc > 3) {  // rare: walk the rest of the head in slot order
+            const uint8_t *h = t.head + (uint64_t)leaf * t.head_bytes;
+            const uint8_t fx = (uint8_t)rep;
+            for (uint32_t sl = c2 + 1; sl < t.cap; ++sl)
+                if (h[sl] == fx && confirm(sl)) break;
+        }
+        ProbeRes r;
+        if (slot >= 0 && !meta_inserting(m) && rid >= meta_cstamp(m) && (nx & kNextKindMask) != kNextCopy) {
+            r.status = ST_LATEST;
+            r.flags = 0;
+            r.hops = 0;
+            r.slot = (uint32_t)slot;
+            r.meta_hi = (uint32_t)(m >> 32);
+            r.cstamp = rid;
+            r.rec_cstamp = meta_cstamp(m);
+            r.copy_sstamp = kMaxCid;
+            r.image = im;
+        } else {
+            visibility(t, slot, m, nx, im, rid, r);
+        }
+        // the chunk's 64 status records, one coalesced 2-KiB (1-KiB) store from their lanes
+        if (valid) {
+            u32x4 a, b;
+            pack_out(leaf, r, a, b);
+            if constexpr (ST == 16) {
+                st16<1>(u32x4{a.x, a.w, b.y, b.x}, reinterpret_cast<uint8_t *>(out) + base * 16u, lane * 16u);
+            } else {
+                uint8_t *ob = reinterpret_cast<uint8_t *>(out + base);
+                st16<1>(a, ob, lane * 32u);
+                st16<1>(b, ob, lane * 32u + 16u);
+            }
+        }
+        if (!recs) continue;
+        // the rows, wave-wide, R in flight
+        const int cnt = (int)((n - base) < 64 ? (n - base) : 64);
+        for (int j0 = 0; j0 < cnt; j0 += R) {
+            for (uint32_t k0 = 0; k0 < out_chunks; k0 += 64) {
+                const uint32_t c = k0 + lane;
+                u32x4 v[R];
+#pragma unroll
+                for (int g = 0; g < R; ++g) {
+                    const uint32_t img = rl32(r.image, j0 + g < cnt ? j0 + g : cnt - 1);
+                    v[g] = u32x4{0, 0, 0, 0};
+                    if (c < out_chunks && img != 0xFFFFFFFFu) v[g] = heap_chunk(t, img, c);
+                }
+#pragma unroll
+                for (int g = 0; g < R; ++g) {
+                    const int j = j0 + g;
+                    if (j < cnt && c < out_chunks) st16<1>(v[g], recs + (base + j) * (uint64_t)t.stride, c * 16u);
+                }
+            }
+        }
+    }
+}
+
 // Chunk-cooperative lower bound of kFirstChunk fixed-width start keys: lane L works for scan
 // L/4 and compares a quarter of each node (4 of the 16 inner entries, 2 of the 8 bottom ones);
 // two xor-shuffles sum the quarter counts.  Same result as tree_lower_bound (le_child = true),
@@ -2660,6 +2784,16 @@ hipError_t launch_probe(const DevTable &t, const uint64_t *keys, const uint16_t 
                 probe_split_kernel<S(), KW(), 64><<<blocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs, d_n);
             }
         });
+        return hipGetLastError();
+    }
+    // the lane-per-probe form (stage_set_probe_form): fixed-width keys at the default group and
+    // store policy; every other shape, and form WAVE, keeps probe_kernel
+    if (!var && tune.form == kProbeFormLane && tune.group == 8 && tune.store == 1 &&
+        (tune.status_bytes != 16 || t.cap == 64)) {
+        auto launch_rows = [&](auto kernel) { kernel<<<blocks, 256, 0, s>>>(t, keys, rids, leaf_in, n, out, recs); };
+        if (tune.status_bytes == 16) launch_rows(probe_rows_kernel<1, kProbeRows, 16>);
+        else if (t.cap == 64) launch_rows(probe_rows_kernel<1, kProbeRows, 32>);
+        else launch_rows(probe_rows_kernel<2, kProbeRows, 32>);
         return hipGetLastError();
     }
     // probe_kernel<VARLEN, SPL, G, POL, ST>: 10 of its 12 instances, the other 2 in launch_probe_fanout

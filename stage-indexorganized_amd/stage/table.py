@@ -594,6 +594,11 @@ class Table:
         check(lib().stage_set_output_layout(self.h, row_stride, status_bytes), "set_output_layout")
         self.status_bytes = status_bytes
 
+    def set_probe_form(self, form):
+        """stage_set_probe_form: 0 = a wave per probe (STAGE_PROBE_FORM_WAVE), 1 = the search a lane
+        per probe, the rows wave-wide (STAGE_PROBE_FORM_LANE)."""
+        check(lib().stage_set_probe_form(self.h, form), "set_probe_form")
+
     def probe_host(self, keys, read_ids=None, lens=None, records=True, out=None, rows=None, window=None):
         """stage_probe_host: the same probe with host-memory inputs and outputs (pipelined).
         `out` / `rows`: caller-owned result arrays (e.g. pinned_empty) to fill instead of new ones;
