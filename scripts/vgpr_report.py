@@ -1,5 +1,5 @@
 """Register report of the kernels in a device assembly file:
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -I include -o k.s csrc/kernels.hip
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -I include -o k.s csrc/probe.hip
     python scripts/vgpr_report.py k.s [name-substring]
 prints VGPRs, SGPRs, SGPR spills into VGPR lanes (v_writelane) and scratch use per kernel --
 the probe's occupancy hinges on it (5 waves/SIMD up to 96 VGPRs, 3 at 154).

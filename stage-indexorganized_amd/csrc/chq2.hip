@@ -36,6 +36,7 @@
 
 #include "handle.hpp"
 #include "visibility.hpp"
+#include "wave.hpp"
 
 using namespace stage_capi;
 
@@ -46,8 +47,6 @@ constexpr int kRegionScan = 6, kNationScan = 65;  // scan_sz of :653 and :734
 constexpr uint32_t kIDataOff = 4 + 32 + 8;         // I_DATA in Item's payload (I_IM_ID, I_NAME, I_PRICE)
 static const char *const kRegions[] = {"AFRICA", "AMERICA", "ASIA", "EUROPE", "MIDDLE EAST"};
 
-__device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ bool produced(uint32_t st) { return st == ST_LATEST || st == ST_COPY || st == ST_OLD; }
 
 __device__ __forceinline__ int32_t ld_i32(const uint8_t *p) {

@@ -22,6 +22,7 @@
 
 #include "../../include/stage_hip.h"
 #include "dist.hpp"
+#include "wave.hpp"
 
 namespace stage {
 
@@ -35,8 +36,6 @@ void nchk(ncclResult_t r, const char *what) {
 }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t rl32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 
 struct alignas(16) SendRec {
     uint64_t key;

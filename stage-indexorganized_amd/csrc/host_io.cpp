@@ -13,7 +13,7 @@
 //    pinned, device-mapped host memory (no separate copies).  While one batch is on the
 //    device the next one fills.
 //  * stage_reader_create_resident: the same adapter with the device side resident
-//    (resident_reader_kernel, kernels.hip) polling a request ring in pinned host memory -- a
+//    (resident_reader_kernel, probe.hip) polling a request ring in pinned host memory -- a
 //    read costs no launch, no event and no thread hand-off, only PCIe round trips.
 #include <hip/hip_runtime_api.h>
 

@@ -1,4 +1,5 @@
-// kernel_api.hpp -- launchers of the gfx950 kernels (kernels.hip), called by the host side.
+// kernel_api.hpp -- launchers of the gfx950 kernels (probe.hip, scan.hip, table_scan.hip,
+// aux_kernels.hip), called by the host side.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -1,5 +1,5 @@
 // visibility.hpp -- device-side version visibility of one hit slot, shared by the probe / scan
-// kernels (kernels.hip) and the kernels that re-evaluate a probe's hit at other read ids inside
+// kernels (probe.hip, scan.hip) and the kernels that re-evaluate a probe's hit at other read ids inside
 // their own pass (chq2.hip: CH-Q2's per-supplier reduce and its finishing kernel).
 #pragma once
 

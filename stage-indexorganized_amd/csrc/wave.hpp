@@ -1,0 +1,33 @@
+// wave.hpp -- gfx950 wave64 lane intrinsics under short names, shared by the library's .hip files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace stage {
+__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ uint32_t rl32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+__device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
+    return ((uint64_t)rl32((uint32_t)(v >> 32), l) << 32) | rl32((uint32_t)v, l);
+}
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// popcount of mask bits below this lane
+__device__ __forceinline__ uint32_t count_below(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// position of the k-th (from 0) set bit of m (m has more than k bits set), per lane
+__device__ __forceinline__ uint32_t kth_set_bit(uint64_t m, uint32_t k) {
+    uint32_t pos = 0;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+        const uint32_t c = (uint32_t)__builtin_popcountll(m & ((1ull << w) - 1));
+        if (k >= c) {
+            k -= c;
+            m >>= w;
+            pos += (uint32_t)w;
+        }
+    }
+    return pos;
+}
+
+}  // namespace stage

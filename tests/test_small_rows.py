@@ -37,6 +37,40 @@ def test_small_rows_layout_matches_oracle(payload, order):
                 np.array([orc.traverse(k.tobytes(), 8, le) for k in probe])).all()
 
 
+def as_keys(values):
+    return np.ascontiguousarray(values, np.uint64).view(np.uint8).reshape(-1, 8)
+
+
+@pytest.mark.gpu
+def test_small_rows_lane_probe_in_256_slot_leaves(gpu):
+    """probe_lane_kernel<4, 1>: 8-byte keys in 256-slot leaves (129..256 records of a 64-KiB leaf),
+    its three confirm rounds and the walk behind the third fingerprint candidate.  keys8's keys are
+    an arithmetic progression, and the fingerprint is a multiplicative hash: it spreads them so
+    evenly that no leaf holds more than three keys of one fingerprint (payloads 240..460, 3900..4096
+    keys, four insertion orders).  So eight keys of one fingerprint that are neighbours in key order
+    (one pair of low bytes, which no other key has) are loaded with them: wherever a leaf boundary
+    falls between the eight, one leaf holds four."""
+    from test_gpu_probe_form import fingerprints
+    from test_gpu_wide_keys import check_wide
+    pool = np.uint64(6001) + (np.arange(1, 6000, dtype=np.uint64) << np.uint64(16))  # 6001: a key of keys8
+    pfp = fingerprints(pool)
+    same = pool[pfp == np.argmax(np.bincount(pfp, minlength=256))]
+    crowd, absent = as_keys(same[:8]), as_keys(same[8:10])
+    keys = np.concatenate([keys8("rand", n=4000), crowd])
+    keys = keys[np.random.default_rng(5).permutation(keys.shape[0])]
+    tab, orc, _ = build(8, 300, keys)
+    assert tab.leaf_capacity == 256
+    tab.sync()
+    rng = np.random.default_rng(300)
+    probe = np.concatenate([crowd, keys[rng.choice(keys.shape[0], 1992, replace=False)],
+                            rng.integers(0, 256, (198, 8), dtype=np.uint8), absent])
+    leaf, kfp = tab.traverse(keys), fingerprints(keys.view(np.uint64).reshape(-1))
+    crowded = [l for l in np.unique(tab.traverse(probe)) if np.bincount(kfp[leaf == l], minlength=256).max() >= 4]
+    assert crowded, "no probed leaf holds four keys of one fingerprint"
+    out = check_wide(tab, orc, probe)
+    assert (out["status"][:2000] == stage.ST_LATEST).all() and (out["status"][-2:] == stage.ST_NOT_FOUND).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("payload,order", CASES)
 def test_small_rows_device_parity(gpu, payload, order):
