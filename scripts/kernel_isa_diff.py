@@ -5,9 +5,11 @@ Compares the gfx950 device code of two built libraries symbol by symbol: the tex
 `llvm-objdump -d` and the kernel descriptor fields of the code objects' metadata.  What depends
 on where the linker put a function is taken out of the text: addresses and encodings, the
 padding after a function's last instruction, and a pc-relative offset to another function
-(replaced by that function's name).  Prints one line per symbol -- same, differs (n lines), only
-in A, only in B -- then every descriptor field that differs, and exits 1 if anything does.  Text
-only: it says whether two builds hold the same instructions, not what they are."""
+(replaced by that function's name).  A device function whose name changed but whose body did not
+-- a symbol only in A and one only in B with equal text -- is paired, and B's name is read as A's
+in the callers.  Prints one line per symbol -- same, same (renamed), differs (n lines), only in A,
+only in B -- then every descriptor field that differs, and exits 1 if anything but a rename does.
+Text only: it says whether two builds hold the same instructions, not what they are."""
 import difflib
 import os
 import re
@@ -60,10 +62,35 @@ def library(path):
     return {k: sorted(v) for k, v in funcs.items()}, descs
 
 
+def pair_renamed(fa, fb):
+    """A's name -> B's name of the one-sided symbols with equal bodies; fb's callers then name A's"""
+    pairs = {}
+    while True:
+        new = {}
+        for nb in sorted(set(fb) - set(fa)):
+            na = next((n for n in sorted(set(fa) - set(fb)) if n not in new and fa[n] == fb[nb]), None)
+            if na is not None:
+                new[na] = nb
+        if not new:
+            return pairs
+        back = {nb: na for na, nb in new.items()}
+        for name, bodies in list(fb.items()):  # a call ends in the callee's name (functions())
+            fb[back.get(name, name)] = sorted(
+                [next((ins[:-len(nb)] + na for nb, na in back.items() if ins.endswith(nb)), ins) for ins in body]
+                for body in bodies)
+            if name in back:
+                del fb[name]
+        pairs.update(new)
+
+
 def main(a, b):
     (fa, da), (fb, db) = library(a), library(b)
+    renamed = pair_renamed(fa, fb)
     changed = 0
     for name in sorted(set(fa) | set(fb)):
+        if name in renamed:
+            print(f"{'same (renamed)':12s} {name} -> {renamed[name]}")
+            continue
         if name not in fb or name not in fa:
             verdict = "only in A" if name in fa else "only in B"
         elif fa[name] == fb[name]:

@@ -3,7 +3,7 @@
 //   * range scan: ballot + mbcnt prefix counts give RangeScanBySize's slot-order truncation
 //     (b_tree.cpp:1276-1302), an in-wave rank sort replaces std::sort, continuation as
 //     Iterator::GetNext (b_tree.h:899-941).
-// scan_one, scan_one_compact and scan_one_window are plain __device__ templates: callers stay here.
+// scan_one and scan_one_compact are plain __device__ templates: callers stay here.
 #include "kernel_api.hpp"
 #include "launch_util.hpp"
 #include "row_store.hpp"
@@ -14,10 +14,47 @@ namespace stage {
 // ----------------------------------------------------------------------------------------
 // range scan (TableScanExecutor over Iterator), one wave per scan
 
-template <bool VARLEN, int SPL, int R, int KW, bool VIS = false>
+// one scan's start: its key length, order-key words and start leaf (wave-uniform)
+template <bool VARLEN, int KW>
+__device__ __forceinline__ uint32_t scan_start(const DevTable &t, const uint64_t *keys, const uint16_t *lens, uint64_t i,
+                                               uint32_t lane, uint64_t *ok, uint32_t &len) {
+    len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+    load_okey<KW>(keys, i, true, len, ok);
+    return uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+}
+
+// the heap row of a kept slot; for VIS the row reader rid sees, its status to row_status[pos].
+// The window forms' snippet: scan_one's row branch and RowSink spell the same lines out, since
+// calling this there (or one helper for their whole row emission) moved the code of the measured
+// scan_kernel instances.
+template <bool VIS>
+__device__ __forceinline__ uint32_t kept_row(const DevTable &t, const SlotInfo &si, uint32_t rid, uint8_t *row_status,
+                                             uint32_t pos) {
+    if (!VIS) return si.image;
+    uint8_t st;
+    const uint32_t img = scan_visible(t, si, rid, st);
+    row_status[pos] = st;
+    return img;
+}
+
+// What a leaf visit does with its e smallest kept records is scan_one's trailing policy: NoWindow
+// copies their rows to recs; ScanWindow (the column-window scan, below) writes their heap rows by
+// rank into the wave's LDS list rk (SPL * 64 words) and hands it to store_scan_windows.  A
+// compile-time policy passed by value: the row instances compile as they did without it.
+struct NoWindow {
+    static constexpr bool on = false;
+};
+struct ScanWindow {
+    static constexpr bool on = true;
+    uint64_t pos0;  // first output position of the scan: i * scan_size
+    uint32_t *rk;
+    const ScanWindowArgs *a;
+};
+
+template <bool VARLEN, int SPL, int R, int KW, bool VIS = false, class Win = NoWindow>
 __device__ void scan_one(const DevTable &t, const uint64_t *x0, uint32_t xl, uint32_t leaf, uint32_t scan_size,
                          uint8_t *recs, uint32_t *count_out, uint32_t lane, uint32_t rid = 0,
-                         uint8_t *row_status = nullptr) {
+                         uint8_t *row_status = nullptr, Win win = {}) {
     uint32_t remaining = scan_size, produced = 0;
     bool cont = false;
     uint64_t x[KW];
@@ -105,35 +142,48 @@ __device__ void scan_one(const DevTable &t, const uint64_t *x0, uint32_t xl, uin
             if (ballot(dup)) break;
         }
         const uint32_t e = m < remaining ? m : remaining;
-        // emit the e smallest kept records at produced + rank, R rows in flight
+        if constexpr (Win::on) {
+            // the e smallest kept records: heap rows into the list by rank (kr < e <= SPL * 64)
 #pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            const bool emit = keep[s] && kr[s] < e;
-            uint32_t img = 0;
-            if (emit) {
-                if (VIS) {
-                    uint8_t st;
-                    img = scan_visible(t, t.slot[base + s * 64 + lane], rid, st);
-                    row_status[produced + kr[s]] = st;
-                } else {
-                    img = t.slot[base + s * 64 + lane].image;
+            for (int s = 0; s < SPL; ++s)
+                if (keep[s] && kr[s] < e)
+                    win.rk[kr[s]] = kept_row<VIS>(t, t.slot[base + s * 64 + lane], rid, row_status, produced + kr[s]);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            store_scan_windows(t, lane, win.pos0 + produced, e, win.rk, *win.a);
+            __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
+        } else {
+            // emit the e smallest kept records at produced + rank, R rows in flight
+#pragma unroll
+            for (int s = 0; s < SPL; ++s) {
+                const bool emit = keep[s] && kr[s] < e;
+                uint32_t img = 0;
+                if (emit) {
+                    if (VIS) {
+                        uint8_t st;
+                        img = scan_visible(t, t.slot[base + s * 64 + lane], rid, st);
+                        row_status[produced + kr[s]] = st;
+                    } else {
+                        img = t.slot[base + s * 64 + lane].image;
+                    }
                 }
-            }
-            uint64_t em = ballot(emit);
-            if (em && t.stride <= 512) {  // small rows: several per load instruction
-                copy_rows_flat<4>(t, em, img, produced + kr[s], recs, lane);
-                em = 0;
-            }
-            while (em) {
-                uint32_t imr[R], dr[R];
-                int nk = 0;
-                for (; nk < R && em; ++nk) {
-                    const int b = __builtin_ctzll(em);
-                    em &= em - 1;
-                    imr[nk] = rl32(img, b);
-                    dr[nk] = produced + rl32(kr[s], b);
+                uint64_t em = ballot(emit);
+                if (em && t.stride <= 512) {  // small rows: several per load instruction
+                    copy_rows_flat<4>(t, em, img, produced + kr[s], recs, lane);
+                    em = 0;
                 }
-                copy_rows<R>(t, imr, dr, nk, recs, lane);
+                while (em) {
+                    uint32_t imr[R], dr[R];
+                    int nk = 0;
+                    for (; nk < R && em; ++nk) {
+                        const int b = __builtin_ctzll(em);
+                        em &= em - 1;
+                        imr[nk] = rl32(img, b);
+                        dr[nk] = produced + rl32(kr[s], b);
+                    }
+                    copy_rows<R>(t, imr, dr, nk, recs, lane);
+                }
             }
         }
         produced += e;
@@ -355,10 +405,9 @@ __device__ __forceinline__ void scan_compact_one(const DevTable &t, const uint64
                                                  uint32_t scan_size, uint32_t *counts, uint8_t *recs,
                                                  const uint32_t *rids, uint8_t *row_status, uint32_t lane,
                                                  uint64_t *s_keys, uint32_t *s_len, uint32_t *s_slot) {
-    const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+    uint32_t len;
     uint64_t ok[KW];
-    load_okey<KW>(keys, i, true, len, ok);
-    const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+    const uint32_t leaf = scan_start<VARLEN, KW>(t, keys, lens, i, lane, ok, len);
     RowSink<VIS> sink{recs + i * (uint64_t)scan_size * t.stride, VIS ? row_status + i * (uint64_t)scan_size : nullptr,
                       VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u};
     const uint32_t produced =
@@ -722,10 +771,9 @@ __global__ __launch_bounds__(256) void scan_kernel(DevTable t, const uint64_t *_
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t i = wave; i < n; i += nwaves) {
-        const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+        uint32_t len;
         uint64_t ok[KW];
-        load_okey<KW>(keys, i, true, len, ok);
-        const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+        const uint32_t leaf = scan_start<VARLEN, KW>(t, keys, lens, i, lane, ok, len);
         scan_one<VARLEN, SPL, R, KW, VIS>(t, ok, len, leaf, scan_size, recs + i * (uint64_t)scan_size * t.stride,
                                           counts + i, lane, VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u,
                                           VIS ? row_status + i * (uint64_t)scan_size : nullptr);
@@ -749,17 +797,7 @@ struct WindowSink {
     template <int KW>
     __device__ __forceinline__ bool emit(const DevTable &t, uint64_t base, bool on, uint32_t mslot, uint32_t kr,
                                          uint32_t produced, const uint64_t *, uint32_t lane) {
-        if (on) {
-            uint32_t img;
-            if (VIS) {
-                uint8_t st;
-                img = scan_visible(t, t.slot[base + mslot], rid, st);
-                row_status[produced + kr] = st;
-            } else {
-                img = t.slot[base + mslot].image;
-            }
-            rk[kr & 63u] = img;
-        }
+        if (on) rk[kr & 63u] = kept_row<VIS>(t, t.slot[base + mslot], rid, row_status, produced + kr);
         const uint32_t e = (uint32_t)__builtin_popcountll(ballot(on));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -782,10 +820,9 @@ __global__ __launch_bounds__(256) void scan_window_kernel_compact(DevTable t, co
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t i = wave; i < n; i += nwaves) {
-        const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+        uint32_t len;
         uint64_t ok[KW];
-        load_okey<KW>(keys, i, true, len, ok);
-        const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
+        const uint32_t leaf = scan_start<VARLEN, KW>(t, keys, lens, i, lane, ok, len);
         WindowSink<VIS> sink{i * (uint64_t)scan_size, VIS ? row_status + i * (uint64_t)scan_size : nullptr,
                              VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u, s_rank[wv], a};
         const uint32_t produced =
@@ -794,139 +831,9 @@ __global__ __launch_bounds__(256) void scan_window_kernel_compact(DevTable t, co
     }
 }
 
-// scan_one with the window writer in place of the row copy: the same collection, ranking and
-// continuation, statement for statement (a device function of its own, so that scan_one's code
-// does not move); the emitting lanes hold (heap row, rank) by slot, the LDS list rk (SPL * 64
-// words, the wave's) turns that into rank order for store_scan_windows.
-template <bool VARLEN, int SPL, int KW, bool VIS>
-__device__ void scan_one_window(const DevTable &t, const uint64_t *x0, uint32_t xl, uint32_t leaf, uint32_t scan_size,
-                                uint64_t pos0, uint32_t *count_out, uint32_t lane, uint32_t rid, uint8_t *row_status,
-                                uint32_t *rk, const ScanWindowArgs &a) {
-    uint32_t remaining = scan_size, produced = 0;
-    bool cont = false;
-    uint64_t x[KW];
-#pragma unroll
-    for (int w = 0; w < KW; ++w) x[w] = x0[w];
-    for (uint32_t guard = 0; guard < scan_size + 2 && remaining > 0; ++guard) {
-        const uint64_t base = (uint64_t)leaf * t.cap;
-        const uint32_t mp =
-            *reinterpret_cast<const uint32_t *>(t.head + (uint64_t)leaf * t.head_bytes + head_info_offset(t.cap, KW)) >> 16;
-        uint64_t col[SPL][KW];
-        uint32_t kl[SPL];
-        uint64_t q[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s)
-#pragma unroll
-            for (int w = 0; w < KW; ++w) col[s][w] = t.okey[((uint64_t)leaf * KW + w) * t.cap + s * 64 + lane];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            const uint64_t vm = head_vis(t, leaf, s);
-            const bool vis = (vm >> lane) & 1;
-            kl[s] = t.key_width;
-            if (VARLEN) kl[s] = vis ? meta_keylen(t.slot[base + s * 64 + lane].meta) : 0u;
-            q[s] = ballot(vis && !key_less<VARLEN, KW>(col[s], kl[s], x, xl));
-        }
-        // slot-order truncation: records are collected until more than to_scan are held
-        const uint32_t to_scan = remaining;
-        uint32_t before = 0, m = 0;
-        bool keep[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            const uint32_t rank = before + count_below(q[s]);
-            keep[s] = ((q[s] >> lane) & 1) && rank <= to_scan;
-            before += (uint32_t)__builtin_popcountll(q[s]);
-        }
-        uint64_t km[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            km[s] = ballot(keep[s]);
-            m += (uint32_t)__builtin_popcountll(km[s]);
-        }
-        if (m == 0) break;
-        // key rank among the kept records: the slot-order position inside the monotone prefix
-        uint32_t kr[SPL];
-        uint32_t top = 0;  // one past the highest kept slot
-#pragma unroll
-        for (int s = 0; s < SPL; ++s)
-            if (km[s]) top = (uint32_t)s * 64u + 64u - (uint32_t)__builtin_clzll(km[s]);
-        const bool mono = top <= mp;
-        {
-            uint32_t pre = 0;
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                kr[s] = mono ? pre + count_below(km[s]) : 0u;
-                pre += (uint32_t)__builtin_popcountll(km[s]);
-            }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < SPL; ++s2) {
-            uint64_t mm = mono ? 0ull : km[s2];
-            while (mm) {
-                const int b = __builtin_ctzll(mm);
-                mm &= mm - 1;
-                uint64_t ko[KW];
-#pragma unroll
-                for (int w = 0; w < KW; ++w) ko[w] = rl64(col[s2][w], b);
-                const uint32_t kll = rl32(kl[s2], b);
-#pragma unroll
-                for (int s = 0; s < SPL; ++s) kr[s] += key_less<VARLEN, KW>(ko, kll, col[s], kl[s]) ? 1u : 0u;
-            }
-        }
-        // continuation: if the new batch starts with the last key, the iterator stops
-        if (cont) {
-            bool dup = false;
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                bool eq = kl[s] == xl;
-#pragma unroll
-                for (int w = 0; w < KW; ++w) eq = eq && col[s][w] == x[w];
-                dup |= keep[s] && kr[s] == 0 && eq;
-            }
-            if (ballot(dup)) break;
-        }
-        const uint32_t e = m < remaining ? m : remaining;
-        // the e smallest kept records: heap rows into the list by rank (kr < e <= SPL * 64)
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            if (keep[s] && kr[s] < e) {
-                uint32_t img;
-                if (VIS) {
-                    uint8_t st;
-                    img = scan_visible(t, t.slot[base + s * 64 + lane], rid, st);
-                    row_status[produced + kr[s]] = st;
-                } else {
-                    img = t.slot[base + s * 64 + lane].image;
-                }
-                rk[kr[s]] = img;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        store_scan_windows(t, lane, pos0 + produced, e, rk, a);
-        __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
-        produced += e;
-        remaining -= e;
-        if (e < m) break;
-        // last record popped: continue from its key with le_child = false (next_leaf_after)
-        uint32_t lastl = 0;
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) {
-            const uint64_t lm = ballot(keep[s] && kr[s] == m - 1);
-            if (lm) {
-                const int b = __builtin_ctzll(lm);
-#pragma unroll
-                for (int w = 0; w < KW; ++w) x[w] = rl64(col[s][w], b);
-                lastl = rl32(kl[s], b);
-            }
-        }
-        xl = lastl;
-        leaf = uni32(next_leaf_after<VARLEN, KW>(t, leaf, x, xl));
-        cont = true;
-    }
-    if (lane == 0) *count_out = produced;
-}
-
+// scan_one with the ScanWindow policy: the row scan's collection, ranking and continuation, one
+// body; the emitting lanes hold (heap row, rank) by slot, the LDS list s_rank (SPL * 64 words per
+// wave) turns that into rank order for store_scan_windows.  R is unused by the window form.
 template <bool VARLEN, int SPL, int KW, bool VIS>
 __global__ __launch_bounds__(256) void scan_window_kernel(DevTable t, const uint64_t *__restrict__ keys,
                                                           const uint16_t *__restrict__ lens, uint64_t n,
@@ -938,13 +845,13 @@ __global__ __launch_bounds__(256) void scan_window_kernel(DevTable t, const uint
     const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
     const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t i = wave; i < n; i += nwaves) {
-        const uint32_t len = t.key_width ? t.key_width : (lens ? (uint32_t)lens[i] : 8u);
+        uint32_t len;
         uint64_t ok[KW];
-        load_okey<KW>(keys, i, true, len, ok);
-        const uint32_t leaf = uni32(resolve_leaf_uniform<VARLEN, KW>(t, ok, len, true, lane));
-        scan_one_window<VARLEN, SPL, KW, VIS>(t, ok, len, leaf, scan_size, i * (uint64_t)scan_size, counts + i, lane,
-                                              VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u,
-                                              VIS ? row_status + i * (uint64_t)scan_size : nullptr, s_rank[wv], a);
+        const uint32_t leaf = scan_start<VARLEN, KW>(t, keys, lens, i, lane, ok, len);
+        scan_one<VARLEN, SPL, 4, KW, VIS>(t, ok, len, leaf, scan_size, nullptr, counts + i, lane,
+                                          VIS ? (rids ? rids[i] : 0xFFFFFFFEu) : 0u,
+                                          VIS ? row_status + i * (uint64_t)scan_size : nullptr,
+                                          ScanWindow{i * (uint64_t)scan_size, s_rank[wv], &a});
     }
 }
 

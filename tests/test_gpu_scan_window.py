@@ -265,10 +265,29 @@ def scan_family(gpu, request):
     else:
         idx = rng.integers(0, base.shape[0], 120)
         srt = base[:5000][np.lexsort(base[:5000].T[::-1])]  # the table's keys in memcmp order
-        starts = np.ascontiguousarray(np.concatenate([base[idx], srt[:1], srt[-1:], srt[-40:-38]]))
+        starts = np.concatenate([base[idx], srt[:1], srt[-1:], srt[-40:-38]])
+        # every key is a visible record and leaves are in key order (keys of 8 bytes order by signed
+        # bytes, wider ones by unsigned bytes), so leaf L holds records [sum(rcnt[:L]), sum(rcnt[:L + 1]))
+        # of the table in key order.  A 100-record scan from the first key of a leaf of more than
+        # 64 records emits min(records of the leaf, 100) > 64 records in its first leaf visit: two
+        # store_windows chunks from the LDS list.
+        tord = base[:5000][np.lexsort((base[:5000].view(np.int8) if base.shape[1] == 8 else base[:5000]).T[::-1])]
+        rcnt, _, _, keyw = tab.export_leaves()
+        assert int(rcnt.sum()) == tord.shape[0]
+        big = np.nonzero(rcnt > 64)[0]
+        assert big.size > 0, f"{request.param}: no leaf holds more than 64 records, the largest holds {rcnt.max()}"
+        lo = (np.cumsum(rcnt) - rcnt)[big[:4]]
+        for L, p in zip(big[:4], lo):  # the leaf's records are those keys (their first 8 bytes)
+            head = np.ascontiguousarray(tord[p:p + rcnt[L], :8]).view(np.uint64).reshape(-1)
+            assert np.array_equal(np.sort(keyw[L, :rcnt[L]]), np.sort(head)), (request.param, L)
+        first = tord[lo]
+        long_visit = np.arange(starts.shape[0], starts.shape[0] + first.shape[0])
+        starts = np.ascontiguousarray(np.concatenate([starts, first]))
         args = dict(start_keys=starts)
-        long_visit = None
-    rids = rng.choice(np.array([5, 11, 13, 16, 20, LAST], np.uint32), len(starts)) if with_rids else None
+    rids = None
+    if with_rids:  # the long-visit starts' read ids are drawn after the others'
+        pool, n0 = np.array([5, 11, 13, 16, 20, LAST], np.uint32), len(starts) - long_visit.size
+        rids = np.concatenate([rng.choice(pool, n0), rng.choice(pool, long_visit.size)])
     return request.param, tab, orc, key_pad, payload, args, rids, long_visit
 
 
@@ -285,10 +304,10 @@ def test_family_scan_windows(scan_family):
                 ln = int(args["lens"][i])
                 c, r = orc.scan(int(starts[i]).to_bytes(8, "little")[:ln], ln, size)
                 oc[i], orows[i, :c] = c, r
-            if size == 100:
-                assert (oc[long_visit] > 64).all()
         else:
             oc, orows = orc.scan_batch_k(starts, size)
+        if size == 100:
+            assert (oc[long_visit] > 64).all(), (name, oc[long_visit])
         c0, rows0 = tab.range_scan(scan_size=size, **args)
         assert np.array_equal(c0, oc)
         assert (oc == size).any()
