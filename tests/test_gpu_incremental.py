@@ -5,6 +5,7 @@ into an existing leaf) only changes slot words and heads of the written leaves; 
 patches those in place on the device (patch_kernel) and appends the new record-heap rows
 and copy/version headers.  After every publish the device must answer exactly like the
 oracle, and a split must fall back to a full re-publish.
+The other leaf geometries and the other write calls: test_gpu_publish_states.py.
 """
 import numpy as np
 import pytest
