@@ -470,7 +470,8 @@ int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, 
  *   An empty range succeeds on a synced table: d_count[0] = 0, d_leaf_offsets[0] = 0.
  *   Every table geometry the scans serve; stage_set_scan_tuning's grid cap applies.  The leaf
  *   counts live in the table's per-call scratch until the work enqueued on `stream` ends.
- *   Not covered: a host-buffer form, predicates or aggregates on the device, sharded forms. */
+ *   Not covered: a host-buffer form, sharded forms.  Predicates and aggregates on the device:
+ *   stage_table_scan_where / stage_table_scan_where_window / stage_table_scan_aggregate below. */
 int stage_table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
                      const uint32_t *read_id,          /* host pointer; NULL = raw */
                      uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
@@ -481,6 +482,76 @@ int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_e
                             uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
                             uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_meta,
                             uint8_t *d_row_status, void *stream);
+/* Whole-table scans with predicates and aggregates evaluated on the device -- the per-tuple
+ *   `predicate` of the reference's executors (executor.h:346-361) applied to the records of
+ *   TableScanExecutor (executor.h:573-642) or, with a read id, of IndexScanExecutor's per-record
+ *   rule (executor.h:465-534).
+ *   A predicate is a closed interval on one little-endian integer column of the payload; up to
+ *   STAGE_PRED_MAX of them are joined by AND.  preds is a HOST pointer, read during the call.
+ *   Match rule, defined against stage_table_scan of the same range and mode (raw, or snapshot at
+ *   *read_id) on the same image: record k of that scan matches iff it yields a tuple
+ *   (d_row_status[k] != STAGE_ST_NOT_FOUND) and every predicate holds on the row bytes the row form
+ *   writes at position k -- the column sits at row byte key_pad + payload_off: the leaf image for
+ *   LATEST, the version's image for OLD, the current image in raw mode.  A record with no tuple
+ *   never matches, under `negate` or with n_pred == 0 either; n_pred == 0: every record that
+ *   yields a tuple matches.  lo > hi is legal: the predicate holds for nothing (for every tuple
+ *   when negated). */
+#define STAGE_PRED_MAX 4
+typedef struct stage_scan_pred {   /* 24 B */
+    uint32_t payload_off;  /* first payload byte of the column ((off, len) convention of stage_update) */
+    uint8_t  width;        /* 1, 2, 4 or 8 bytes, little-endian, at any alignment               */
+    uint8_t  is_signed;    /* 0: zero-extended and compared as uint64; 1: sign-extended, int64   */
+    uint8_t  negate;       /* 0: holds iff lo <= x <= hi;  1: holds iff not                      */
+    uint8_t  pad;          /* 0                                                                  */
+    int64_t  lo, hi;       /* in the column's domain (unsigned column: the uint64 bit patterns)  */
+} stage_scan_pred;
+typedef struct stage_scan_agg {    /* 32 B, device memory */
+    uint64_t count;        /* matching records                                                   */
+    int64_t  sum;          /* of the extended values, modulo 2^64                                */
+    int64_t  min, max;     /* in the column's domain; count == 0: min = the domain's largest
+                              value, max = its smallest; sum = 0                                 */
+} stage_scan_agg;
+/* stage_table_scan_where / _where_window (executor.h:346-361, 465-534, 573-642): the matching
+ *   records in the unfiltered scan's order, compacted.  d_count[0] = the number of matches,
+ *   whatever max_records cut off; d_leaf_offsets[i] = the position of leaf leaf_begin + i's first
+ *   match, the closing entry = the count; rows, windows, keys, meta and status are exactly what
+ *   the unfiltered form holds for those records; d_row_slot (optional, one u64 per record) =
+ *   (leaf index in key order << 16) | slot, the numbering of stage_probe_out.leaf / .slot.
+ *   Truncation at max_records, count-only calls (max_records == 0, null record buffers),
+ *   leaf_end == UINT64_MAX, alignment, "nothing at or past max_records is touched", the resume
+ *   rule from d_leaf_offsets and stage_set_scan_tuning's grid cap are those of stage_table_scan*.
+ *   STAGE_E_ARG, checked before the table's "needs stage_sync" state: null table, n_pred >
+ *   STAGE_PRED_MAX, null preds with n_pred != 0, a width outside {1, 2, 4, 8}, payload_off +
+ *   width > payload_size, is_signed or negate above 1, pad != 0, and the range, buffer and window
+ *   errors of stage_table_scan*.  Then STAGE_E_STATE for a stale image, then the leaf-count
+ *   check.  An empty range succeeds: d_count[0] = 0, d_leaf_offsets[0] = 0.
+ *   Per call the table's scratch holds 4 nl + 8 ceil(nl / 64) + 8 (cap / 64) nl bytes for nl
+ *   leaves of cap slots (about 25 MB at 100M YCSB rows: one bit per slot, the matches per leaf
+ *   and per tile of 64 leaves) until the work enqueued on `stream` ends.
+ * stage_table_scan_aggregate (executor.h:346-361, 465-534, 573-642): d_agg[0] = count, sum, min
+ *   and max of the matching records' column (agg_off, agg_width, agg_signed) -- the column
+ *   convention of stage_scan_pred; agg_width == 0: the count alone, sum = min = max = 0.  Integer
+ *   and order-free, so bit-exact whatever the grid.  No record output.  Errors as above, for the
+ *   predicates and for the aggregate column (agg_signed above 1 too), and null d_agg.  An empty
+ *   range gives count 0 and the identities.  Scratch: one 32-B partial per workgroup.
+ *   Not covered: group-by, byte-string and LIKE predicates, disjunctions, predicates on key
+ *   bytes, host-buffer and sharded forms. */
+int stage_table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                           const uint32_t *read_id,          /* host pointer; NULL = raw */
+                           const stage_scan_pred *preds,     /* host pointer */
+                           uint32_t n_pred, uint64_t max_records, uint64_t *d_count,
+                           uint64_t *d_leaf_offsets, uint8_t *d_records, uint64_t *d_row_slot,
+                           uint64_t *d_row_meta, uint8_t *d_row_status, void *stream);
+int stage_table_scan_where_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                                  const uint32_t *read_id, const stage_scan_pred *preds,
+                                  uint32_t n_pred, uint32_t payload_off, uint32_t len,
+                                  uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
+                                  uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_slot,
+                                  uint64_t *d_row_meta, uint8_t *d_row_status, void *stream);
+int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                               const uint32_t *read_id, const stage_scan_pred *preds,
+                               uint32_t n_pred, uint32_t agg_off, uint32_t agg_width /* 0 = count only */,
+                               uint32_t agg_signed, stage_scan_agg *d_agg, void *stream);
 /* The IndexScanExecutor range branch of stage_index_scan_batch consumed only up to its first
  * produced tuple (LATEST or OLD) whose key begins with the start key's first `prefix_words`
  * 8-byte fields (0..key_words) -- the predicate TPC-C stock-level puts on its ORDER_LINE scans

@@ -706,6 +706,126 @@ int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_e
                       d_window, d_row_keys, d_row_meta, d_row_status, stream);
 }
 
+static_assert(sizeof(stage_scan_pred) == 24 && sizeof(stage_scan_agg) == 32, "stage_hip.h layout");
+static_assert(STAGE_PRED_MAX == stage::kScanPredMax, "stage_hip.h mirrors kernel_api.hpp");
+
+// one integer column (payload_off, width) against the table's parameters alone
+static int check_column(stage_table *t, const char *what, uint32_t payload_off, uint32_t width) {
+    if (width != 1 && width != 2 && width != 4 && width != 8)
+        return fail(STAGE_E_ARG, std::string(what) + ": width must be 1, 2, 4 or 8");
+    if ((uint64_t)payload_off + width > facts(t).params().payload_size)
+        return fail(STAGE_E_ARG, std::string(what) + ": payload_off + width exceeds the table's payload_size");
+    return STAGE_OK;
+}
+
+// the predicates of a filtered scan, checked without a device image and turned into row-byte form
+static int check_preds(stage_table *t, const stage_scan_pred *preds, uint32_t n_pred, stage::ScanPreds &out) {
+    if (!t) return fail(STAGE_E_ARG, "null table");
+    if (n_pred > STAGE_PRED_MAX) return fail(STAGE_E_ARG, "predicates: n_pred exceeds STAGE_PRED_MAX");
+    if (n_pred && !preds) return fail(STAGE_E_ARG, "predicates: null preds with n_pred != 0");
+    out = stage::ScanPreds{};
+    out.n = n_pred;
+    for (uint32_t k = 0; k < n_pred; ++k) {
+        const stage_scan_pred &p = preds[k];
+        int rc = check_column(t, "predicate", p.payload_off, p.width);
+        if (rc) return rc;
+        if (p.is_signed > 1 || p.negate > 1) return fail(STAGE_E_ARG, "predicate: is_signed and negate are 0 or 1");
+        if (p.pad != 0) return fail(STAGE_E_ARG, "predicate: pad must be 0");
+        out.p[k] = stage::ScanPred{facts(t).key_pad() + p.payload_off, p.width, p.is_signed, p.negate, 0, p.lo, p.hi};
+    }
+    return STAGE_OK;
+}
+
+// the leaf range of a table scan against the published image (after need_synced)
+static int resolve_leaf_range(stage_table *t, uint64_t leaf_begin, uint64_t &leaf_end) {
+    const uint64_t nleaves = t->dev.view.nleaves;
+    if (leaf_end == UINT64_MAX) leaf_end = nleaves;
+    if (leaf_end > nleaves || leaf_begin > leaf_end)
+        return fail(STAGE_E_ARG, "table scan: the leaf range exceeds the table's " + std::to_string(nleaves) + " leaves");
+    return STAGE_OK;
+}
+
+// both filtered whole-table scans (the per-tuple predicate of executor.h:346-361 on the records of
+// TableScanExecutor, executor.h:573-642 / IndexScanExecutor's rule, executor.h:465-534)
+static int table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                            const stage_scan_pred *preds, uint32_t n_pred, bool window, uint32_t payload_off,
+                            uint32_t len, uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
+                            uint8_t *d_out, uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta,
+                            uint8_t *d_row_status, void *stream) {
+    stage::ScanPreds p;
+    int rc = check_preds(t, preds, n_pred, p);
+    if (rc) return rc;
+    rc = window ? check_window(t, payload_off, len) : STAGE_OK;
+    if (rc) return rc;
+    if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
+    if (!d_count) return fail(STAGE_E_ARG, "table scan: null d_count");
+    if (max_records && !d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
+    rc = need_synced(t);
+    if (rc) return rc;
+    rc = resolve_leaf_range(t, leaf_begin, leaf_end);
+    if (rc) return rc;
+    return guarded([&] {
+        hipError_t e = hipSetDevice(t->dev.device);
+        if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
+        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
+        uint8_t *scratch =
+            nl ? stage::scratch_bytes(t->dev, stage::table_scan_where_scratch_bytes(nl, t->dev.view.cap)) : nullptr;
+        const stage::TableScanOut o{max_records, d_count, d_leaf_offsets, window ? nullptr : d_out,
+                                    window ? d_out : nullptr, window ? d_row_keys : nullptr, d_row_meta, d_row_status};
+        e = stage::launch_table_scan_where(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr,
+                                           read_id ? *read_id : 0u, p, window ? facts(t).key_pad() + payload_off : 0u,
+                                           window ? len : 0u, facts(t).key_pad(), o, d_row_slot, scratch,
+                                           pick(t, stream), t->scan_tune);
+        return hip_rc(e, "filtered table scan kernels");
+    });
+}
+
+int stage_table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                           const stage_scan_pred *preds, uint32_t n_pred, uint64_t max_records, uint64_t *d_count,
+                           uint64_t *d_leaf_offsets, uint8_t *d_records, uint64_t *d_row_slot, uint64_t *d_row_meta,
+                           uint8_t *d_row_status, void *stream) {
+    return table_scan_where(t, leaf_begin, leaf_end, read_id, preds, n_pred, false, 0, 0, max_records, d_count,
+                            d_leaf_offsets, d_records, nullptr, d_row_slot, d_row_meta, d_row_status, stream);
+}
+
+int stage_table_scan_where_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                                  const stage_scan_pred *preds, uint32_t n_pred, uint32_t payload_off, uint32_t len,
+                                  uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_window,
+                                  uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta,
+                                  uint8_t *d_row_status, void *stream) {
+    return table_scan_where(t, leaf_begin, leaf_end, read_id, preds, n_pred, true, payload_off, len, max_records,
+                            d_count, d_leaf_offsets, d_window, d_row_keys, d_row_slot, d_row_meta, d_row_status, stream);
+}
+
+int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                               const stage_scan_pred *preds, uint32_t n_pred, uint32_t agg_off, uint32_t agg_width,
+                               uint32_t agg_signed, stage_scan_agg *d_agg, void *stream) {
+    stage::ScanPreds p;
+    int rc = check_preds(t, preds, n_pred, p);
+    if (rc) return rc;
+    rc = agg_width ? check_column(t, "aggregate column", agg_off, agg_width) : STAGE_OK;
+    if (rc) return rc;
+    if (agg_signed > 1) return fail(STAGE_E_ARG, "aggregate column: agg_signed is 0 or 1");
+    if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
+    if (!d_agg) return fail(STAGE_E_ARG, "table scan: null d_agg");
+    rc = need_synced(t);
+    if (rc) return rc;
+    rc = resolve_leaf_range(t, leaf_begin, leaf_end);
+    if (rc) return rc;
+    return guarded([&] {
+        hipError_t e = hipSetDevice(t->dev.device);
+        if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
+        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
+        uint8_t *scratch =
+            nl ? stage::scratch_bytes(t->dev, stage::table_scan_aggregate_scratch_bytes(nl, t->scan_tune)) : nullptr;
+        e = stage::launch_table_scan_aggregate(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr,
+                                               read_id ? *read_id : 0u, p, facts(t).key_pad() + agg_off, agg_width,
+                                               agg_signed != 0, reinterpret_cast<uint64_t *>(d_agg), scratch,
+                                               pick(t, stream), t->scan_tune);
+        return hip_rc(e, "table scan aggregate kernels");
+    });
+}
+
 int stage_index_scan_first_batch(stage_table *t, const uint64_t *d_start_keys, const uint32_t *d_read_ids,
                                  uint64_t n, uint32_t scan_size, uint32_t prefix_words, uint32_t *d_image,
                                  uint8_t *d_status, void *stream) {

@@ -129,6 +129,38 @@ uint64_t table_scan_scratch_bytes(uint64_t nl);
 hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
                              uint32_t row_off, uint32_t len, uint32_t key_pad, const TableScanOut &o, uint8_t *scratch,
                              hipStream_t s, const ScanTuning &tune);
+// Filtered whole-table scans.  A record of launch_table_scan's set (same range, same mode) matches
+// when it yields a tuple (status != ST_NOT_FOUND) and every predicate holds on its heap row: the
+// column of `width` (1, 2, 4, 8) little-endian bytes at row byte `src` (key pad + payload offset),
+// sign- or zero-extended, lies in [lo, hi] (negate: does not).  The predicates travel by value
+// in the kernel arguments.
+constexpr uint32_t kScanPredMax = 4;
+struct ScanPred {  // 24 B
+    uint32_t src;
+    uint8_t width, is_signed, negate, pad;
+    int64_t lo, hi;  // the column's domain (unsigned column: the uint64 bit patterns)
+};
+struct ScanPreds {
+    uint32_t n, pad;
+    ScanPred p[kScanPredMax];
+};
+// launch_table_scan's outputs for the matching records alone, compacted in the same order (o's
+// fields and every rule of launch_table_scan), row_slot (optional): (leaf << 16) | slot per
+// record.  scratch: table_scan_where_scratch_bytes(nl, t.cap) bytes (tile offsets, one bit per
+// slot, matches per leaf), 8-B aligned.  Four launches (match, tile sums, offsets, emit).
+uint64_t table_scan_where_scratch_bytes(uint64_t nl, uint32_t cap);
+hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                   const ScanPreds &preds, uint32_t row_off, uint32_t len, uint32_t key_pad,
+                                   const TableScanOut &o, uint64_t *row_slot, uint8_t *scratch, hipStream_t s,
+                                   const ScanTuning &tune);
+// agg[0..3] = {count, sum modulo 2^64, min, max} of the matching records' column (agg_src,
+// agg_width, agg_signed), the words of stage_scan_agg; agg_width 0: the count alone (sum, min,
+// max zero).  Integer and order-free, so the result does not depend on the grid.  scratch:
+// table_scan_aggregate_scratch_bytes(nl, tune) bytes (one 32-B partial per block).
+uint64_t table_scan_aggregate_scratch_bytes(uint64_t nl, const ScanTuning &tune);
+hipError_t launch_table_scan_aggregate(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                       const ScanPreds &preds, uint32_t agg_src, uint32_t agg_width, bool agg_signed,
+                                       uint64_t *agg, uint8_t *scratch, hipStream_t s, const ScanTuning &tune);
 // two single scans (no read id) of two tables in one launch, the same records as launch_scan of
 // each (n = 1): 8-byte keys, leaves of the same size above 128 slots, 1..63 records each
 // (scan_pair_supported; otherwise hipErrorInvalidValue and nothing is launched)

@@ -1,4 +1,5 @@
-// table_scan.hip -- gfx950 kernels of the whole-table scan (count, offsets, emit) and their launcher.
+// table_scan.hip -- gfx950 kernels of the whole-table scan (count, offsets, emit), of its filtered
+// forms (match, emit from the match bits) and of the aggregate, and their launchers.
 #include "kernel_api.hpp"
 #include "launch_util.hpp"
 #include "row_store.hpp"
@@ -263,6 +264,375 @@ hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, boo
             else table_scan_emit_kernel<false, false><<<blocks, 256, 0, s>>>(t, g);
         }
     }
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------------------
+// filtered whole-table scans (stage_table_scan_where / _where_window / _aggregate): the records
+// of the unfiltered scan that yield a tuple and on whose row bytes every predicate holds --
+// the per-tuple predicate of TableScanExecutor / IndexScanExecutor (executor.h:346-361, 465-534,
+// 573-642) evaluated on the device.  The same three stream-ordered steps: a match pass that
+// stores one bit per slot and the matches per leaf, the offsets of the tile sums
+// (table_scan_offsets_kernel, as it is), and an emit pass whose emitting lanes are the stored
+// bits.  The aggregate runs the match pass's loop alone and keeps count / sum / min / max in
+// registers.  Integer arithmetic only, no atomics, no workgroup waits for another.
+
+// column `width` bytes at row byte src of heap row img, little-endian at any alignment, zero-
+// extended: out of the one or two aligned 8-B words that hold it.  The second word is read only
+// when the column's last byte lies in it, and that byte is below src + width <= key pad +
+// payload <= hstride (a multiple of 16), so no load leaves the row's own hstride bytes.
+__device__ __forceinline__ uint64_t column_bits(const DevTable &t, uint32_t img, uint32_t src, uint32_t width) {
+    const uint64_t *row = reinterpret_cast<const uint64_t *>(t.heap + (uint64_t)img * t.hstride);
+    const uint32_t w = src >> 3, sh = uni32(src & 7u);
+    uint64_t x = row[w] >> (8u * sh);
+    if (sh + width > 8u) x |= row[w + 1u] << (8u * (8u - sh));  // sh >= 1 here
+    return width >= 8u ? x : x & ((1ull << (8u * width)) - 1ull);
+}
+
+// the column's value in a domain where unsigned order is the column's order: the sign-extended
+// value with its top bit flipped (signed), the zero-extended value (unsigned)
+__device__ __forceinline__ uint64_t column_key(uint64_t bits, uint32_t width, bool is_signed) {
+    if (!is_signed) return bits;
+    const uint32_t up = 64u - 8u * width;
+    return (uint64_t)((int64_t)(bits << up) >> up) ^ (1ull << 63);
+}
+
+// every predicate on heap row img (wave-uniform predicates, kernel arguments)
+__device__ __forceinline__ bool preds_hold(const DevTable &t, uint32_t img, const ScanPreds &p) {
+    bool ok = true;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPredMax; ++k)
+        if (k < p.n) {
+            const ScanPred &q = p.p[k];
+            const uint64_t x = column_key(column_bits(t, img, q.src, q.width), q.width, q.is_signed != 0);
+            // lo / hi arrive in the same order domain (launch_table_scan_where flips a signed column's)
+            const bool in = x >= (uint64_t)q.lo && x <= (uint64_t)q.hi;
+            ok &= in != (q.negate != 0);
+        }
+    return ok;
+}
+
+// one 64-slot group of a leaf: the lanes the head names (snapshot) or the lanes below the record
+// count (raw) read their slot word and resolve the image; -> the lane's heap row, 0xFFFFFFFF
+// when the lane's slot is not part of the scan or yields no tuple
+template <bool VIS>
+__device__ __forceinline__ uint32_t scan_group_image(const DevTable &t, uint32_t leaf, uint32_t s, uint32_t lane,
+                                                     uint32_t rc, uint32_t rid) {
+    const bool on = VIS ? ((head_vis(t, leaf, (int)s) >> lane) & 1) != 0 : s * 64u + lane < rc;
+    uint32_t img = 0xFFFFFFFFu;
+    if (on) {
+        const SlotInfo si = t.slot[(uint64_t)leaf * t.cap + s * 64u + lane];
+        uint8_t st;
+        if (VIS) img = scan_visible(t, si, rid, st);
+        else if (si.meta != 0) img = si.image;
+    }
+    return img;
+}
+
+template <bool VIS>
+__device__ __forceinline__ uint32_t scan_record_count(const DevTable &t, uint32_t leaf) {
+    if (VIS) return t.cap;
+    const uint32_t rc = uni32(*reinterpret_cast<const uint32_t *>(t.head + (uint64_t)leaf * t.head_bytes +
+                                                                  head_info_offset(t.cap, t.key_words)) & 0xFFFFu);
+    return rc > t.cap ? t.cap : rc;
+}
+
+// the match pass, a wave per leaf: mask[i * (cap / 64) + s] = the matching lanes of leaf i's
+// slot group s, cnt[i] = their number
+template <bool VIS>
+__global__ __launch_bounds__(256) void table_scan_match_kernel(DevTable t, uint32_t leaf0, uint32_t nl, uint32_t rid,
+                                                               ScanPreds p, uint64_t *__restrict__ mask,
+                                                               uint32_t *__restrict__ cnt) {
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t spl = t.cap >> 6;
+    for (uint64_t i = wave; i < nl; i += nwaves) {
+        const uint32_t leaf = leaf0 + (uint32_t)i;
+        const uint32_t rc = scan_record_count<VIS>(t, leaf);
+        uint32_t total = 0;
+        for (uint32_t s = 0; s < spl; ++s) {
+            uint64_t m = 0;
+            if (s * 64u < rc) {
+                const uint32_t img = scan_group_image<VIS>(t, leaf, s, lane, rc, rid);
+                m = ballot(img != 0xFFFFFFFFu && preds_hold(t, img, p));
+            }
+            if (lane == 0) mask[i * spl + s] = m;
+            total += (uint32_t)__builtin_popcountll(m);
+        }
+        if (lane == 0) cnt[i] = total;
+    }
+}
+
+// the sums of cnt over tiles of 64 leaves, a wave per tile and a lane per leaf
+__global__ __launch_bounds__(256) void table_scan_tile_sums_kernel(const uint32_t *__restrict__ cnt, uint32_t nl,
+                                                                   uint64_t *__restrict__ tsum) {
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint64_t ntiles = ((uint64_t)nl + 63) >> 6;
+    for (uint64_t k = wave; k < ntiles; k += nwaves) {
+        const uint64_t i = k * 64 + lane;
+        uint32_t c = i < nl ? cnt[i] : 0u;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+        if (lane == 0) tsum[k] = c;
+    }
+}
+
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
+
+// what a filtered emit launch carries beside the emit pass's arguments (wave-uniform)
+struct TableScanWhereArgs {
+    TableScanArgs g;
+    const uint64_t *mask;  // [nl * cap / 64] the match pass's bits
+    uint64_t *row_slot;    // optional: (leaf << 16) | slot per record
+};
+
+// table_scan_emit_kernel with the emitting lanes taken from the match pass's bits: the matched
+// lanes read their slot word again and resolve image and status again (the same image: the
+// passes are stream-ordered on one published image), rank themselves, and the leaf's matches
+// leave through the same store paths.  A leaf without a match costs its mask words.
+template <bool VIS, bool WIN>
+__global__ __launch_bounds__(256) void table_scan_emit_where_kernel(DevTable t, TableScanWhereArgs a) {
+    __shared__ uint32_t s_img[4][kTableScanMaxCap];
+    const TableScanArgs &g = a.g;
+    const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
+    uint32_t *rk = s_img[wv];
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t spl = t.cap >> 6;
+    for (uint64_t i = wave; i < g.nl; i += nwaves) {
+        const uint32_t leaf = g.leaf0 + (uint32_t)i;
+        const uint64_t base = (uint64_t)leaf * t.cap;
+        const uint64_t tile = i >> 6;
+        const uint32_t self = (uint32_t)(i & 63u);
+        const uint32_t c = lane <= self ? g.cnt[tile * 64 + lane] : 0u;
+        const uint64_t tile0 = g.toff[tile];
+        uint64_t mk = uni64(a.mask[i * spl]);
+        const uint32_t own = rl32(c, (int)self);
+        uint32_t v = lane < self ? c : 0u;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+        const uint64_t pos0 = tile0 + uni32(v);
+        if (g.leaf_offsets && lane == 0) g.leaf_offsets[i] = pos0;
+        if (own == 0 || pos0 >= g.max_records) continue;
+        uint32_t produced = 0;
+        for (uint32_t s = 0; s < spl; ++s) {
+            if (s) mk = uni64(a.mask[i * spl + s]);
+            if (mk == 0) continue;
+            const bool on = ((mk >> lane) & 1) != 0;
+            if (on) {
+                const SlotInfo si = t.slot[base + s * 64u + lane];
+                uint8_t st = ST_LATEST;
+                const uint32_t img = VIS ? scan_visible(t, si, g.rid, st) : si.image;
+                const uint32_t r = produced + count_below(mk);  // < cap
+                rk[r] = img;
+                const uint64_t k = pos0 + r;
+                if (k < g.max_records) {
+                    if (g.row_meta) g.row_meta[k] = si.meta;
+                    if (g.row_status) g.row_status[k] = st;
+                    if (a.row_slot) a.row_slot[k] = ((uint64_t)leaf << 16) | (s * 64u + lane);
+                }
+            }
+            produced += (uint32_t)__builtin_popcountll(mk);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint64_t room = g.max_records - pos0;
+        const uint32_t e = produced < room ? produced : (uint32_t)room;
+        if (WIN) store_scan_windows(t, lane, pos0, e, rk, g.a);
+        else store_scan_rows(t, lane, pos0, e, rk, g.recs);
+        __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
+    }
+}
+
+// count / sum / min / max of one block's (or the fold's) lanes: over the wave by shuffles, over
+// the block's waves through LDS; thread 0 holds the result.  min / max travel in the unsigned
+// order domain of column_key.
+struct AggAcc {
+    uint64_t count, sum, min, max;
+};
+__device__ __forceinline__ void agg_add(AggAcc &a, const AggAcc &b) {
+    a.count += b.count;
+    a.sum += b.sum;
+    a.min = b.min < a.min ? b.min : a.min;
+    a.max = b.max > a.max ? b.max : a.max;
+}
+__device__ __forceinline__ void agg_block_reduce(AggAcc &a, AggAcc *s_part) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        AggAcc b;
+        b.count = (uint64_t)__shfl_xor((unsigned long long)a.count, o, 64);
+        b.sum = (uint64_t)__shfl_xor((unsigned long long)a.sum, o, 64);
+        b.min = (uint64_t)__shfl_xor((unsigned long long)a.min, o, 64);
+        b.max = (uint64_t)__shfl_xor((unsigned long long)a.max, o, 64);
+        agg_add(a, b);
+    }
+    const uint32_t wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63u) == 0) s_part[wv] = a;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (uint32_t k = 1; k < nw; ++k) agg_add(a, s_part[k]);
+}
+
+// the aggregate column of a launch (wave-uniform); width 0: count only
+struct ScanAggCol {
+    uint32_t src, width, is_signed;
+};
+
+// the match pass's loop with the aggregate column read beside the predicate columns; each block
+// leaves one partial (order-domain min / max) in part[blockIdx.x]
+template <bool VIS>
+__global__ __launch_bounds__(256) void table_scan_aggregate_kernel(DevTable t, uint32_t leaf0, uint32_t nl,
+                                                                   uint32_t rid, ScanPreds p, ScanAggCol col,
+                                                                   AggAcc *__restrict__ part) {
+    __shared__ AggAcc s_part[4];
+    const uint32_t lane = lane_id();
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + uni32(threadIdx.x >> 6);
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t spl = t.cap >> 6;
+    AggAcc acc{0, 0, ~0ull, 0};
+    for (uint64_t i = wave; i < nl; i += nwaves) {
+        const uint32_t leaf = leaf0 + (uint32_t)i;
+        const uint32_t rc = scan_record_count<VIS>(t, leaf);
+        for (uint32_t s = 0; s < spl && s * 64u < rc; ++s) {
+            const uint32_t img = scan_group_image<VIS>(t, leaf, s, lane, rc, rid);
+            if (img != 0xFFFFFFFFu && preds_hold(t, img, p)) {
+                acc.count += 1;
+                if (col.width) {
+                    const uint64_t x = column_key(column_bits(t, img, col.src, col.width), col.width, col.is_signed != 0);
+                    acc.sum += col.is_signed ? x ^ (1ull << 63) : x;  // the extended value, modulo 2^64
+                    acc.min = x < acc.min ? x : acc.min;
+                    acc.max = x > acc.max ? x : acc.max;
+                }
+            }
+        }
+    }
+    agg_block_reduce(acc, s_part);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// one block folds the partials into agg[0] = {count, sum, min, max} in the column's domain;
+// no match (or no partial at all): min = the domain's largest value, max = its smallest
+__global__ __launch_bounds__(256) void table_scan_aggregate_fold_kernel(const AggAcc *__restrict__ part, uint32_t nparts,
+                                                                        ScanAggCol col, uint64_t *__restrict__ agg) {
+    __shared__ AggAcc s_part[4];
+    AggAcc acc{0, 0, ~0ull, 0};
+    for (uint32_t k = threadIdx.x; k < nparts; k += blockDim.x) agg_add(acc, part[k]);
+    agg_block_reduce(acc, s_part);
+    if (threadIdx.x != 0) return;
+    uint64_t mn = 0, mx = 0;
+    if (col.width) {
+        const uint64_t flip = col.is_signed ? 1ull << 63 : 0ull;
+        if (acc.count) {
+            mn = acc.min ^ flip;
+            mx = acc.max ^ flip;
+        } else {
+            const uint64_t ones = col.width >= 8u ? ~0ull : (1ull << (8u * col.width)) - 1ull;
+            mn = col.is_signed ? ones >> 1 : ones;   // 2^(8w-1) - 1, or 2^(8w) - 1
+            mx = col.is_signed ? ~(ones >> 1) : 0ull;  // -2^(8w-1), or 0
+        }
+    }
+    agg[0] = acc.count;
+    agg[1] = acc.sum;
+    agg[2] = mn;
+    agg[3] = mx;
+}
+
+// a signed column's bounds enter the order domain of column_key once, on the host
+static ScanPreds order_domain(ScanPreds p) {
+    for (uint32_t k = 0; k < p.n; ++k)
+        if (p.p[k].is_signed) {
+            p.p[k].lo = (int64_t)((uint64_t)p.p[k].lo ^ (1ull << 63));
+            p.p[k].hi = (int64_t)((uint64_t)p.p[k].hi ^ (1ull << 63));
+        }
+    return p;
+}
+
+static bool preds_fit(const DevTable &t, const ScanPreds &p) {
+    if (p.n > kScanPredMax) return false;
+    for (uint32_t k = 0; k < p.n; ++k) {
+        const uint32_t w = p.p[k].width;
+        if ((w != 1 && w != 2 && w != 4 && w != 8) || (uint64_t)p.p[k].src + w > t.hstride) return false;
+    }
+    return true;
+}
+
+uint64_t table_scan_where_scratch_bytes(uint64_t nl, uint32_t cap) {
+    return ((nl + 63) / 64) * 8 + nl * (cap / 64) * 8 + nl * 4;
+}
+
+hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                   const ScanPreds &preds, uint32_t row_off, uint32_t len, uint32_t key_pad,
+                                   const TableScanOut &o, uint64_t *row_slot, uint8_t *scratch, hipStream_t s,
+                                   const ScanTuning &tune) {
+    const bool win = len != 0;
+    // launch_table_scan's conditions, and every predicate column inside a heap row (column_bits'
+    // loads rest on it)
+    if ((uint64_t)leaf0 + nl > t.nleaves || t.cap > kTableScanMaxCap || !o.count || !preds_fit(t, preds))
+        return hipErrorInvalidValue;
+    if (win && ((uint64_t)row_off + len > t.hstride || key_pad > t.hstride || (key_pad & 7u))) return hipErrorInvalidValue;
+    if (o.max_records && !(win ? o.win : o.recs)) return hipErrorInvalidValue;
+    if (nl == 0) {
+        hipError_t e = hipMemsetAsync(o.count, 0, sizeof(uint64_t), s);
+        if (e == hipSuccess && o.leaf_offsets) e = hipMemsetAsync(o.leaf_offsets, 0, sizeof(uint64_t), s);
+        return e;
+    }
+    if (!scratch) return hipErrorInvalidValue;
+    const uint64_t ntiles = ((uint64_t)nl + 63) / 64;
+    uint64_t *toff = reinterpret_cast<uint64_t *>(scratch);
+    uint64_t *mask = toff + ntiles;
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(mask + (uint64_t)nl * (t.cap / 64));
+    const int mb = max_blocks(tune);
+    const int blocks = grid_for(nl, 4, mb);
+    const ScanPreds p = order_domain(preds);
+    if (snapshot) table_scan_match_kernel<true><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
+    else table_scan_match_kernel<false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
+    table_scan_tile_sums_kernel<<<grid_for(ntiles, 4, mb), 256, 0, s>>>(cnt, nl, toff);
+    table_scan_offsets_kernel<<<1, 1024, 0, s>>>(toff, ntiles, o.count, o.leaf_offsets ? o.leaf_offsets + nl : nullptr);
+    if (o.max_records || o.leaf_offsets) {
+        const TableScanWhereArgs a{
+            TableScanArgs{leaf0, nl, cnt, toff, o.max_records, o.leaf_offsets, o.row_meta, o.row_status, o.recs,
+                          ScanWindowArgs{WindowArgs{row_off, len, (len + 15u) >> 4, o.win}, o.row_keys, key_pad}, rid},
+            mask, row_slot};
+        if (snapshot) {
+            if (win) table_scan_emit_where_kernel<true, true><<<blocks, 256, 0, s>>>(t, a);
+            else table_scan_emit_where_kernel<true, false><<<blocks, 256, 0, s>>>(t, a);
+        } else {
+            if (win) table_scan_emit_where_kernel<false, true><<<blocks, 256, 0, s>>>(t, a);
+            else table_scan_emit_where_kernel<false, false><<<blocks, 256, 0, s>>>(t, a);
+        }
+    }
+    return hipGetLastError();
+}
+
+// the match pass's grid: a partial per block is 32 B of scratch, and a grid of a few blocks per
+// CU (2048, measured at 100M rows) left a tail of blocks that no longer fit beside the first wave
+static int aggregate_blocks(uint32_t nl, const ScanTuning &tune) { return grid_for(nl, 4, max_blocks(tune)); }
+
+uint64_t table_scan_aggregate_scratch_bytes(uint64_t nl, const ScanTuning &tune) {
+    return nl ? (uint64_t)aggregate_blocks((uint32_t)nl, tune) * sizeof(AggAcc) : 0;
+}
+
+hipError_t launch_table_scan_aggregate(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                       const ScanPreds &preds, uint32_t agg_src, uint32_t agg_width, bool agg_signed,
+                                       uint64_t *agg, uint8_t *scratch, hipStream_t s, const ScanTuning &tune) {
+    if ((uint64_t)leaf0 + nl > t.nleaves || !agg || !preds_fit(t, preds)) return hipErrorInvalidValue;
+    if (agg_width && ((agg_width != 1 && agg_width != 2 && agg_width != 4 && agg_width != 8) ||
+                      (uint64_t)agg_src + agg_width > t.hstride))
+        return hipErrorInvalidValue;
+    if (nl && !scratch) return hipErrorInvalidValue;
+    const ScanAggCol col{agg_src, agg_width, agg_signed ? 1u : 0u};
+    AggAcc *part = reinterpret_cast<AggAcc *>(scratch);
+    const int blocks = nl ? aggregate_blocks(nl, tune) : 0;
+    if (nl) {
+        const ScanPreds p = order_domain(preds);
+        if (snapshot) table_scan_aggregate_kernel<true><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, col, part);
+        else table_scan_aggregate_kernel<false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, col, part);
+    }
+    table_scan_aggregate_fold_kernel<<<1, 256, 0, s>>>(part, (uint32_t)blocks, col, agg);
     return hipGetLastError();
 }
 

@@ -27,6 +27,26 @@ class StageParams(ctypes.Structure):
     ]
 
 
+class ScanPred(ctypes.Structure):
+    """stage_scan_pred"""
+    _fields_ = [
+        ("payload_off", ctypes.c_uint32),
+        ("width", ctypes.c_uint8),
+        ("is_signed", ctypes.c_uint8),
+        ("negate", ctypes.c_uint8),
+        ("pad", ctypes.c_uint8),
+        ("lo", ctypes.c_int64),
+        ("hi", ctypes.c_int64),
+    ]
+
+
+class ScanAgg(ctypes.Structure):
+    """stage_scan_agg"""
+    _fields_ = [("count", ctypes.c_uint64), ("sum", ctypes.c_int64), ("min", ctypes.c_int64), ("max", ctypes.c_int64)]
+
+
+PRED_MAX = 4  # STAGE_PRED_MAX
+
 # every exported symbol: name -> (restype, argtypes)
 SIGNATURES = {
     "stage_last_error": (ctypes.c_char_p, []),
@@ -134,6 +154,14 @@ SIGNATURES = {
     "stage_table_scan_window": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, ctypes.c_uint32,
                                                ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_vp]),
+    "stage_table_scan_where": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_uint32,
+                                              ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "stage_table_scan_where_window": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
+                                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                     c_vp]),
+    "stage_table_scan_aggregate": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_uint32,
+                                                  ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
     "stage_resolve_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, c_vp, c_vp]),
     "stage_set_probe_tuning": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
     "stage_set_scan_tuning": (ctypes.c_int, [c_vp, ctypes.c_int]),

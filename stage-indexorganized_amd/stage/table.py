@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import StageParams, c_vp, check, lib
+from ._lib import ScanAgg, ScanPred, StageParams, c_vp, check, lib
 
 PROBE_OUT_DTYPE = np.dtype([
     ("status", "u1"), ("flags", "u1"), ("hops", "u2"), ("leaf", "u4"), ("slot", "u2"), ("key_len", "u2"),
@@ -39,6 +39,41 @@ RC_NOT_NEEDED_UPDATE, RC_DIRTY = 7, 9
 # stage_table_scan: "through the last leaf", and what Table.table_scan returns
 LEAF_END = 0xFFFFFFFFFFFFFFFF
 TableScanResult = collections.namedtuple("TableScanResult", "count offsets records keys meta status")
+# Table.table_scan_where: table_scan's fields for the matching records, and slots[m] =
+# (leaf index in key order << 16) | slot of each (row_slot=True)
+TableScanWhereResult = collections.namedtuple("TableScanWhereResult", TableScanResult._fields + ("slots",))
+
+
+class Pred(collections.namedtuple("Pred", "off width lo hi signed negate")):
+    """One predicate of a filtered table scan (stage_scan_pred): the little-endian integer column
+    of `width` (1, 2, 4, 8) bytes at payload offset `off`, sign- or zero-extended, lies in
+    [lo, hi] -- or, with negate, does not.  lo and hi are Python ints in the column's domain (an
+    unsigned 8-byte column: up to 2**64 - 1)."""
+    __slots__ = ()
+
+    def __new__(cls, off, width, lo, hi, signed=False, negate=False):
+        return super().__new__(cls, int(off), int(width), int(lo), int(hi), bool(signed), bool(negate))
+
+
+def _i64(v):
+    """the int64 with v's low 64 bits (a uint64 bit pattern as stage_scan_pred.lo / .hi take it)"""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _pack_preds(preds):
+    """-> (ctypes array of stage_scan_pred or None, n_pred); the array must outlive the call"""
+    preds = [p if isinstance(p, (Pred, ScanPred)) else Pred(*p) for p in (preds or ())]
+    if not preds:
+        return None, 0
+    arr = (ScanPred * len(preds))()
+    for a, p in zip(arr, preds):
+        if isinstance(p, ScanPred):
+            ctypes.memmove(ctypes.byref(a), ctypes.byref(p), ctypes.sizeof(ScanPred))
+        else:
+            a.payload_off, a.width, a.is_signed, a.negate = p.off, p.width, int(p.signed), int(p.negate)
+            a.lo, a.hi = _i64(p.lo), _i64(p.hi)
+    return arr, len(preds)
 
 
 def _ptr(a):
@@ -779,6 +814,84 @@ class Table:
                                d_out.to_numpy(np.uint8, m * width).reshape(m, width),
                                d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
                                d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m))
+
+    def table_scan_where_device(self, leaves, read_id, preds, max_records, d_count, d_leaf_offsets=None, d_out=None,
+                                window=None, d_row_keys=None, d_row_slot=None, d_row_meta=None, d_row_status=None,
+                                stream=None):
+        """stage_table_scan_where (window None) / stage_table_scan_where_window on device buffers:
+        table_scan_device's arguments, preds = a sequence of Pred (at most 4, all must hold; empty:
+        every record that yields a tuple), d_row_slot one u64 per record.  Enqueued on `stream`."""
+        def p(b):
+            return getattr(b, "ptr", b)
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        arr, n = _pack_preds(preds)
+        if window is None:
+            check(lib().stage_table_scan_where(self.h, begin, end, rid, arr, n, max_records, p(d_count),
+                                               p(d_leaf_offsets), p(d_out), p(d_row_slot), p(d_row_meta),
+                                               p(d_row_status), p(stream)), "stage_table_scan_where")
+        else:
+            check(lib().stage_table_scan_where_window(self.h, begin, end, rid, arr, n, window[0], window[1], max_records,
+                                                      p(d_count), p(d_leaf_offsets), p(d_out), p(d_row_keys),
+                                                      p(d_row_slot), p(d_row_meta), p(d_row_status), p(stream)),
+                  "stage_table_scan_where_window")
+
+    def table_scan_where(self, leaves=None, read_id=None, preds=(), window=None, row_keys=False, row_meta=False,
+                         row_slot=False, max_records=None):
+        """table_scan kept to the records that yield a tuple and on which every Pred of `preds`
+        holds, in the same order, compacted.  Returns TableScanWhereResult: table_scan's fields
+        (count = the matches of the range, offsets = the position of each leaf's first match) and
+        slots[m] = (leaf << 16) | slot with row_slot=True."""
+        if row_keys and window is None:
+            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+        d_cnt = DeviceBuffer(8)
+        self.table_scan_where_device((begin, end), read_id, preds, 0, d_cnt, window=window)
+        check(lib().stage_device_sync(), "sync")
+        count = int(d_cnt.to_numpy(np.uint64, 1)[0])
+        if end == LEAF_END:
+            end = self.stats()["leaves"]
+        m = count if max_records is None else min(count, int(max_records))
+        width = self.stride if window is None else window_stride(window[1])
+        d_off = DeviceBuffer((end - begin + 1) * 8)
+        d_out = DeviceBuffer(max(1, m * width))
+        d_key = DeviceBuffer(max(1, m * self.key_pad)) if row_keys else None
+        d_slot = DeviceBuffer(max(1, m * 8)) if row_slot else None
+        d_meta = DeviceBuffer(max(1, m * 8)) if row_meta else None
+        d_st = DeviceBuffer(max(1, m))
+        self.table_scan_where_device((begin, end), read_id, preds, m, d_cnt, d_off, d_out, window, d_key, d_slot,
+                                     d_meta, d_st)
+        check(lib().stage_device_sync(), "sync")
+        return TableScanWhereResult(
+            int(d_cnt.to_numpy(np.uint64, 1)[0]), d_off.to_numpy(np.uint64, end - begin + 1),
+            d_out.to_numpy(np.uint8, m * width).reshape(m, width),
+            d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
+            d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m),
+            d_slot.to_numpy(np.uint64, m) if row_slot else None)
+
+    def table_scan_aggregate_device(self, leaves, read_id, preds, agg, d_agg, stream=None):
+        """stage_table_scan_aggregate into d_agg (32 bytes of device memory: count, sum, min, max);
+        agg = (payload_off, width, signed) or None for the count alone.  Enqueued on `stream`."""
+        def p(b):
+            return getattr(b, "ptr", b)
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        arr, n = _pack_preds(preds)
+        off, width, signed = (0, 0, False) if agg is None else agg
+        check(lib().stage_table_scan_aggregate(self.h, begin, end, rid, arr, n, off, width, int(signed), p(d_agg),
+                                               p(stream)), "stage_table_scan_aggregate")
+
+    def table_scan_aggregate(self, leaves=None, read_id=None, preds=(), agg=None):
+        """(count, sum, min, max) of column agg = (payload_off, width, signed) over the records
+        table_scan_where selects, as Python ints in the column's domain (sum modulo 2**64: of an
+        unsigned column in [0, 2**64), of a signed one in [-2**63, 2**63)); no match: min = the
+        domain's largest value, max = its smallest.  agg None: the count, and zeros."""
+        d_agg = DeviceBuffer(32)
+        self.table_scan_aggregate_device(leaves, read_id, preds, agg, d_agg)
+        check(lib().stage_device_sync(), "sync")
+        w = d_agg.to_numpy(np.uint64, 4)
+        signed = agg is not None and bool(agg[2])
+        return (int(w[0]),) + tuple(_i64(int(x)) if signed else int(x) for x in w[1:])
 
     def index_scan_first(self, start_keys, scan_size, prefix_words, read_ids=None):
         """index_scan consumed up to its first LATEST / OLD tuple carrying the start key's first
