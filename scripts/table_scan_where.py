@@ -12,6 +12,10 @@ timed with device events in alternating rounds --
     agg, agg_p10        stage_table_scan_aggregate of column (0, 4) without a predicate and under
                         the 10 % predicate
 
+--read-id R runs every shape in snapshot mode at read id R (the kernels' VIS instances) instead
+of raw mode.  STAGE_LIB=<another build's libstage_hip.so> times that build: alternate the two
+for an A/B.
+
 Prints one JSON line (and appends it to --out): per shape min / median / max and the per-round
 times, the matches, bytes per scanned record by construction with the resulting bytes/s beside the
 achievable HBM rate (6.3 TB/s; reported, not a gate), and two comparisons: whether the aggregate's
@@ -78,7 +82,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--out", default=None, help="file the JSON line is appended to")
+    ap.add_argument("--read-id", type=lambda v: int(v, 0), default=None,
+                    help="snapshot mode at this read id (the VIS kernel instances); default: raw mode")
     args = ap.parse_args()
+    rid = args.read_id
     assert args.rounds >= 1 and args.steps >= 1 and args.rows >= 1000
     if stage.device_count() < 1:
         raise SystemExit("no HIP device: this script measures on the GPU only")
@@ -100,14 +107,14 @@ def main():
     d_slot = stage.DeviceBuffer(rows * 8)
 
     # ---- the unfiltered scans: what every filtered result is checked against
-    tab.table_scan_device(None, None, rows, d_cnt, None, d_out, W4, d_key, stream=s)
+    tab.table_scan_device(None, rid, rows, d_cnt, None, d_out, W4, d_key, stream=s)
     s.sync()
     total = int(d_cnt.to_numpy(np.uint64, 1)[0])
     assert total == rows, (total, rows)
     keys = d_key.to_numpy(np.uint64, total, stream=s.ptr)
     col = np.ascontiguousarray(d_out.to_numpy(np.uint8, total * ws4, stream=s.ptr).reshape(total, ws4)[:, :4]) \
         .view(np.uint32).reshape(-1)
-    tab.table_scan_device(None, None, rows, d_cnt, None, d_out, W100, stream=s)
+    tab.table_scan_device(None, rid, rows, d_cnt, None, d_out, W100, stream=s)
     s.sync()
     win100 = d_out.to_numpy(np.uint8, total * ws100, stream=s.ptr).reshape(total, ws100)
     order = np.sort(col)
@@ -121,14 +128,14 @@ def main():
         return p + [stage.Pred(COL2[0], COL2[1], 0, 0xFFFFFFFF)] if two else p
 
     def where(f, two, keys_too=False):
-        return lambda: tab.table_scan_where_device(None, None, preds(f, two), rows, d_cnt, None, d_out, W100,
+        return lambda: tab.table_scan_where_device(None, rid, preds(f, two), rows, d_cnt, None, d_out, W100,
                                                    d_key if keys_too else None, d_slot if keys_too else None, stream=s)
 
     def agg(p):
-        return lambda: tab.table_scan_aggregate_device(None, None, p, COL, d_agg, stream=s)
+        return lambda: tab.table_scan_aggregate_device(None, rid, p, COL, d_agg, stream=s)
 
-    shapes = {"win4": (lambda: tab.table_scan_device(None, None, rows, d_cnt, None, d_out, W4, stream=s), [COL], None, 1.0),
-              "win100": (lambda: tab.table_scan_device(None, None, rows, d_cnt, None, d_out, W100, stream=s), [], W100, 1.0)}
+    shapes = {"win4": (lambda: tab.table_scan_device(None, rid, rows, d_cnt, None, d_out, W4, stream=s), [COL], None, 1.0),
+              "win100": (lambda: tab.table_scan_device(None, rid, rows, d_cnt, None, d_out, W100, stream=s), [], W100, 1.0)}
     matches = {}
     for two in (False, True):
         for f in FRACTIONS:
@@ -214,10 +221,10 @@ def main():
     ok = all(all(c.values()) for c in check.values())
     line = json.dumps({
         "script": "table_scan_where", "rows": rows, "leaves": nl, "records_per_leaf": round(total / nl, 2),
-        "rounds": args.rounds, "steps_per_round": args.steps, "window": W100, "predicate_column": COL,
+        "rounds": args.rounds, "steps_per_round": args.steps, "read_id": rid, "window": W100, "predicate_column": COL,
         "second_predicate_column": COL2, "thresholds": thresholds, "matches": matches, "device": device,
         "comparisons": compare, "hbm_achievable_tb_s": HBM_ACHIEVABLE / 1e12, "check_equal": check,
-        "version": stage.lib().stage_version().decode()})
+        "version": stage.lib().stage_version().decode(), "lib": os.environ.get("STAGE_LIB") or "this tree"})
     print(line, flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

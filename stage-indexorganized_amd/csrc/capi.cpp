@@ -659,60 +659,12 @@ int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, 
                        d_row_keys, d_row_status, true, stream);
 }
 
-// both whole-table scans (TableScanExecutor, executor.h:573-642; per record IndexScanExecutor's
-// rule, executor.h:465-534): `window` selects the window form, d_out is d_records / d_window
-static int table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id, bool window,
-                      uint32_t payload_off, uint32_t len, uint64_t max_records, uint64_t *d_count,
-                      uint64_t *d_leaf_offsets, uint8_t *d_out, uint8_t *d_row_keys, uint64_t *d_row_meta,
-                      uint8_t *d_row_status, void *stream) {
-    if (!t) return fail(STAGE_E_ARG, "null table");
-    int rc = window ? check_window(t, payload_off, len) : STAGE_OK;
-    if (rc) return rc;
-    if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
-    if (!d_count) return fail(STAGE_E_ARG, "table scan: null d_count");
-    if (max_records && !d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
-    rc = need_synced(t);
-    if (rc) return rc;
-    const uint64_t nleaves = t->dev.view.nleaves;
-    if (leaf_end == UINT64_MAX) leaf_end = nleaves;
-    if (leaf_end > nleaves || leaf_begin > leaf_end)
-        return fail(STAGE_E_ARG, "table scan: the leaf range exceeds the table's " + std::to_string(nleaves) + " leaves");
-    return guarded([&] {
-        hipError_t e = hipSetDevice(t->dev.device);
-        if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
-        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
-        uint8_t *scratch = nl ? stage::scratch_bytes(t->dev, stage::table_scan_scratch_bytes(nl)) : nullptr;
-        const stage::TableScanOut o{max_records, d_count, d_leaf_offsets, window ? nullptr : d_out,
-                                    window ? d_out : nullptr, window ? d_row_keys : nullptr, d_row_meta, d_row_status};
-        e = stage::launch_table_scan(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr, read_id ? *read_id : 0u,
-                                     window ? facts(t).key_pad() + payload_off : 0u, window ? len : 0u,
-                                     facts(t).key_pad(), o, scratch, pick(t, stream), t->scan_tune);
-        return hip_rc(e, "table scan kernels");
-    });
-}
-
-int stage_table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
-                     uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_records,
-                     uint64_t *d_row_meta, uint8_t *d_row_status, void *stream) {
-    return table_scan(t, leaf_begin, leaf_end, read_id, false, 0, 0, max_records, d_count, d_leaf_offsets, d_records,
-                      nullptr, d_row_meta, d_row_status, stream);
-}
-
-int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
-                            uint32_t payload_off, uint32_t len, uint64_t max_records, uint64_t *d_count,
-                            uint64_t *d_leaf_offsets, uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_meta,
-                            uint8_t *d_row_status, void *stream) {
-    return table_scan(t, leaf_begin, leaf_end, read_id, true, payload_off, len, max_records, d_count, d_leaf_offsets,
-                      d_window, d_row_keys, d_row_meta, d_row_status, stream);
-}
-
 static_assert(sizeof(stage_scan_pred) == 24 && sizeof(stage_scan_agg) == 32, "stage_hip.h layout");
 static_assert(STAGE_PRED_MAX == stage::kScanPredMax, "stage_hip.h mirrors kernel_api.hpp");
 
 // one integer column (payload_off, width) against the table's parameters alone
 static int check_column(stage_table *t, const char *what, uint32_t payload_off, uint32_t width) {
-    if (width != 1 && width != 2 && width != 4 && width != 8)
-        return fail(STAGE_E_ARG, std::string(what) + ": width must be 1, 2, 4 or 8");
+    if (!stage::scan_column_width(width)) return fail(STAGE_E_ARG, std::string(what) + ": width must be 1, 2, 4 or 8");
     if ((uint64_t)payload_off + width > facts(t).params().payload_size)
         return fail(STAGE_E_ARG, std::string(what) + ": payload_off + width exceeds the table's payload_size");
     return STAGE_OK;
@@ -745,21 +697,45 @@ static int resolve_leaf_range(stage_table *t, uint64_t leaf_begin, uint64_t &lea
     return STAGE_OK;
 }
 
-// both filtered whole-table scans (the per-tuple predicate of executor.h:346-361 on the records of
-// TableScanExecutor, executor.h:573-642 / IndexScanExecutor's rule, executor.h:465-534)
-static int table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
-                            const stage_scan_pred *preds, uint32_t n_pred, bool window, uint32_t payload_off,
-                            uint32_t len, uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets,
-                            uint8_t *d_out, uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta,
-                            uint8_t *d_row_status, void *stream) {
-    stage::ScanPreds p;
-    int rc = check_preds(t, preds, n_pred, p);
+// What a whole-table scan entry point asks for besides the leaf range and the read id.
+struct TableScanWindow {  // the window form's payload bytes
+    uint32_t payload_off, len;
+};
+struct TableScanAggColumn {  // the aggregate's column; width 0: the count alone
+    uint32_t payload_off, width, is_signed;
+};
+struct TableScanRequest {
+    bool filtered;                  // the _where forms and the aggregate: preds / n_pred are checked
+    const stage_scan_pred *preds;
+    uint32_t n_pred;
+    const TableScanAggColumn *agg;  // null: the scan delivers records
+    const TableScanWindow *window;  // null: rows
+    const void *d_result;           // d_count, or d_agg with an aggregate column
+    uint64_t max_records;           // records: a record buffer must come with max_records != 0
+    const void *d_out;
+    const char *kernels;            // names the launch in a HIP error
+};
+// launch(first leaf, leaves, snapshot mode, read id, the predicates in row-byte form)
+using TableScanLaunch = std::function<hipError_t(uint32_t, uint32_t, bool, uint32_t, const stage::ScanPreds &)>;
+
+// Every whole-table scan entry point (TableScanExecutor, executor.h:573-642; per record
+// IndexScanExecutor's rule, executor.h:465-534; the per-tuple predicate of executor.h:346-361):
+// the argument checks in one order -- predicates, aggregate column, window, leaf range, result
+// word, record buffer -- then, on the published image and the table's device, the launch.
+static int table_scan_call(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                           const TableScanRequest &q, const TableScanLaunch &launch) {
+    if (!t) return fail(STAGE_E_ARG, "null table");
+    stage::ScanPreds p{};
+    int rc = q.filtered ? check_preds(t, q.preds, q.n_pred, p) : STAGE_OK;
     if (rc) return rc;
-    rc = window ? check_window(t, payload_off, len) : STAGE_OK;
+    rc = q.agg && q.agg->width ? check_column(t, "aggregate column", q.agg->payload_off, q.agg->width) : STAGE_OK;
+    if (rc) return rc;
+    if (q.agg && q.agg->is_signed > 1) return fail(STAGE_E_ARG, "aggregate column: agg_signed is 0 or 1");
+    rc = q.window ? check_window(t, q.window->payload_off, q.window->len) : STAGE_OK;
     if (rc) return rc;
     if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
-    if (!d_count) return fail(STAGE_E_ARG, "table scan: null d_count");
-    if (max_records && !d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
+    if (!q.d_result) return fail(STAGE_E_ARG, q.agg ? "table scan: null d_agg" : "table scan: null d_count");
+    if (q.max_records && !q.d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
     rc = need_synced(t);
     if (rc) return rc;
     rc = resolve_leaf_range(t, leaf_begin, leaf_end);
@@ -767,25 +743,58 @@ static int table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_e
     return guarded([&] {
         hipError_t e = hipSetDevice(t->dev.device);
         if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
-        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
-        uint8_t *scratch =
-            nl ? stage::scratch_bytes(t->dev, stage::table_scan_where_scratch_bytes(nl, t->dev.view.cap)) : nullptr;
+        e = launch((uint32_t)leaf_begin, (uint32_t)(leaf_end - leaf_begin), read_id != nullptr, read_id ? *read_id : 0u, p);
+        return hip_rc(e, q.kernels);
+    });
+}
+
+// the four scans that deliver records: `filtered` selects the _where forms, a window the window
+// forms, d_out is d_records / d_window
+static int table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id, bool filtered,
+                      const stage_scan_pred *preds, uint32_t n_pred, const TableScanWindow *window,
+                      uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_out,
+                      uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta, uint8_t *d_row_status,
+                      void *stream) {
+    const TableScanRequest q{filtered, preds, n_pred, nullptr, window, d_count, max_records, d_out,
+                             filtered ? "filtered table scan kernels" : "table scan kernels"};
+    return table_scan_call(t, leaf_begin, leaf_end, read_id, q,
+                           [&](uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid, const stage::ScanPreds &p) {
+        const uint64_t bytes = filtered ? stage::table_scan_where_scratch_bytes(nl, t->dev.view.cap)
+                                        : stage::table_scan_scratch_bytes(nl);
+        uint8_t *scratch = nl ? stage::scratch_bytes(t->dev, bytes) : nullptr;
         const stage::TableScanOut o{max_records, d_count, d_leaf_offsets, window ? nullptr : d_out,
                                     window ? d_out : nullptr, window ? d_row_keys : nullptr, d_row_meta, d_row_status};
-        e = stage::launch_table_scan_where(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr,
-                                           read_id ? *read_id : 0u, p, window ? facts(t).key_pad() + payload_off : 0u,
-                                           window ? len : 0u, facts(t).key_pad(), o, d_row_slot, scratch,
-                                           pick(t, stream), t->scan_tune);
-        return hip_rc(e, "filtered table scan kernels");
+        const uint32_t kp = facts(t).key_pad(), row_off = window ? kp + window->payload_off : 0u;
+        const uint32_t len = window ? window->len : 0u;
+        return filtered ? stage::launch_table_scan_where(t->dev.view, leaf0, nl, snapshot, rid, p, row_off, len, kp, o,
+                                                         d_row_slot, scratch, pick(t, stream), t->scan_tune)
+                        : stage::launch_table_scan(t->dev.view, leaf0, nl, snapshot, rid, row_off, len, kp, o, scratch,
+                                                   pick(t, stream), t->scan_tune);
     });
+}
+
+int stage_table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                     uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_records,
+                     uint64_t *d_row_meta, uint8_t *d_row_status, void *stream) {
+    return table_scan(t, leaf_begin, leaf_end, read_id, false, nullptr, 0, nullptr, max_records, d_count, d_leaf_offsets,
+                      d_records, nullptr, nullptr, d_row_meta, d_row_status, stream);
+}
+
+int stage_table_scan_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                            uint32_t payload_off, uint32_t len, uint64_t max_records, uint64_t *d_count,
+                            uint64_t *d_leaf_offsets, uint8_t *d_window, uint8_t *d_row_keys, uint64_t *d_row_meta,
+                            uint8_t *d_row_status, void *stream) {
+    const TableScanWindow w{payload_off, len};
+    return table_scan(t, leaf_begin, leaf_end, read_id, false, nullptr, 0, &w, max_records, d_count, d_leaf_offsets,
+                      d_window, d_row_keys, nullptr, d_row_meta, d_row_status, stream);
 }
 
 int stage_table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
                            const stage_scan_pred *preds, uint32_t n_pred, uint64_t max_records, uint64_t *d_count,
                            uint64_t *d_leaf_offsets, uint8_t *d_records, uint64_t *d_row_slot, uint64_t *d_row_meta,
                            uint8_t *d_row_status, void *stream) {
-    return table_scan_where(t, leaf_begin, leaf_end, read_id, preds, n_pred, false, 0, 0, max_records, d_count,
-                            d_leaf_offsets, d_records, nullptr, d_row_slot, d_row_meta, d_row_status, stream);
+    return table_scan(t, leaf_begin, leaf_end, read_id, true, preds, n_pred, nullptr, max_records, d_count,
+                      d_leaf_offsets, d_records, nullptr, d_row_slot, d_row_meta, d_row_status, stream);
 }
 
 int stage_table_scan_where_window(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
@@ -793,36 +802,23 @@ int stage_table_scan_where_window(stage_table *t, uint64_t leaf_begin, uint64_t 
                                   uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_window,
                                   uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta,
                                   uint8_t *d_row_status, void *stream) {
-    return table_scan_where(t, leaf_begin, leaf_end, read_id, preds, n_pred, true, payload_off, len, max_records,
-                            d_count, d_leaf_offsets, d_window, d_row_keys, d_row_slot, d_row_meta, d_row_status, stream);
+    const TableScanWindow w{payload_off, len};
+    return table_scan(t, leaf_begin, leaf_end, read_id, true, preds, n_pred, &w, max_records, d_count, d_leaf_offsets,
+                      d_window, d_row_keys, d_row_slot, d_row_meta, d_row_status, stream);
 }
 
 int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
                                const stage_scan_pred *preds, uint32_t n_pred, uint32_t agg_off, uint32_t agg_width,
                                uint32_t agg_signed, stage_scan_agg *d_agg, void *stream) {
-    stage::ScanPreds p;
-    int rc = check_preds(t, preds, n_pred, p);
-    if (rc) return rc;
-    rc = agg_width ? check_column(t, "aggregate column", agg_off, agg_width) : STAGE_OK;
-    if (rc) return rc;
-    if (agg_signed > 1) return fail(STAGE_E_ARG, "aggregate column: agg_signed is 0 or 1");
-    if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
-    if (!d_agg) return fail(STAGE_E_ARG, "table scan: null d_agg");
-    rc = need_synced(t);
-    if (rc) return rc;
-    rc = resolve_leaf_range(t, leaf_begin, leaf_end);
-    if (rc) return rc;
-    return guarded([&] {
-        hipError_t e = hipSetDevice(t->dev.device);
-        if (e != hipSuccess) return hip_rc(e, "hipSetDevice");
-        const uint32_t nl = (uint32_t)(leaf_end - leaf_begin);
-        uint8_t *scratch =
-            nl ? stage::scratch_bytes(t->dev, stage::table_scan_aggregate_scratch_bytes(nl, t->scan_tune)) : nullptr;
-        e = stage::launch_table_scan_aggregate(t->dev.view, (uint32_t)leaf_begin, nl, read_id != nullptr,
-                                               read_id ? *read_id : 0u, p, facts(t).key_pad() + agg_off, agg_width,
-                                               agg_signed != 0, reinterpret_cast<uint64_t *>(d_agg), scratch,
-                                               pick(t, stream), t->scan_tune);
-        return hip_rc(e, "table scan aggregate kernels");
+    const TableScanAggColumn col{agg_off, agg_width, agg_signed};
+    const TableScanRequest q{true, preds, n_pred, &col, nullptr, d_agg, 0, nullptr, "table scan aggregate kernels"};
+    return table_scan_call(t, leaf_begin, leaf_end, read_id, q,
+                           [&](uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid, const stage::ScanPreds &p) {
+        const uint64_t bytes = stage::table_scan_aggregate_scratch_bytes(nl, t->scan_tune);
+        uint8_t *scratch = nl ? stage::scratch_bytes(t->dev, bytes) : nullptr;
+        return stage::launch_table_scan_aggregate(t->dev.view, leaf0, nl, snapshot, rid, p, facts(t).key_pad() + agg_off,
+                                                  agg_width, agg_signed != 0, reinterpret_cast<uint64_t *>(d_agg), scratch,
+                                                  pick(t, stream), t->scan_tune);
     });
 }
 

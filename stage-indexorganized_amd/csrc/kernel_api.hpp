@@ -135,6 +135,7 @@ hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, boo
 // sign- or zero-extended, lies in [lo, hi] (negate: does not).  The predicates travel by value
 // in the kernel arguments.
 constexpr uint32_t kScanPredMax = 4;
+constexpr bool scan_column_width(uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8; }
 struct ScanPred {  // 24 B
     uint32_t src;
     uint8_t width, is_signed, negate, pad;
@@ -147,7 +148,8 @@ struct ScanPreds {
 // launch_table_scan's outputs for the matching records alone, compacted in the same order (o's
 // fields and every rule of launch_table_scan), row_slot (optional): (leaf << 16) | slot per
 // record.  scratch: table_scan_where_scratch_bytes(nl, t.cap) bytes (tile offsets, one bit per
-// slot, matches per leaf), 8-B aligned.  Four launches (match, tile sums, offsets, emit).
+// slot, matches per leaf), 8-B aligned.  Four launches (match, tile sums, then launch_table_scan's
+// offsets and emit kernels: one launcher body and one emit kernel serve both).
 uint64_t table_scan_where_scratch_bytes(uint64_t nl, uint32_t cap);
 hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
                                    const ScanPreds &preds, uint32_t row_off, uint32_t len, uint32_t key_pad,

@@ -1,5 +1,5 @@
-// table_scan.hip -- gfx950 kernels of the whole-table scan (count, offsets, emit), of its filtered
-// forms (match, emit from the match bits) and of the aggregate, and their launchers.
+// table_scan.hip -- gfx950 kernels of the whole-table scan and of its filtered forms (a count or a
+// match pass, the offsets, one emit pass for both) and of the aggregate, and their launchers.
 #include "kernel_api.hpp"
 #include "launch_util.hpp"
 #include "row_store.hpp"
@@ -19,11 +19,14 @@ namespace stage {
 // workgroup waits for another: records per leaf and their sums over tiles of 64 leaves
 // (table_scan_count_kernel), an exclusive scan of the tile sums by one block
 // (table_scan_offsets_kernel), and the emit pass, where a leaf's wave adds the counts of its
-// tile's earlier leaves (one 256-B load) to the tile's offset.
+// tile's earlier leaves (one 256-B load) to the tile's offset.  The filtered forms (further down)
+// replace the first step by a match pass and run the other two as they are.
 constexpr uint32_t kTableScanMaxCap = 1024;  // slots per leaf the emit pass's LDS list holds
 
-// what an emit launch carries (wave-uniform)
+// what an emit launch carries (wave-uniform); the type also selects the emitting lanes at compile
+// time: every slot of the scan here, the match pass's bits with TableScanMatchArgs
 struct TableScanArgs {
+    static constexpr bool matched = false;
     uint32_t leaf0, nl;      // the range: leaves leaf0 .. leaf0 + nl - 1
     const uint32_t *cnt;     // [nl] records per leaf
     const uint64_t *toff;    // [(nl + 63) / 64] position of each tile's first record
@@ -34,6 +37,11 @@ struct TableScanArgs {
     uint8_t *recs;           // row form: rows of t.stride bytes
     ScanWindowArgs a;        // window form
     uint32_t rid;            // snapshot mode: the read id
+};
+struct TableScanMatchArgs : TableScanArgs {
+    static constexpr bool matched = true;
+    const uint64_t *mask;  // [nl * cap / 64] the match pass's bits
+    uint64_t *row_slot;    // optional: (leaf << 16) | slot per record
 };
 
 // records per leaf of the range and their sums over tiles of 64 leaves, a wave per tile and a
@@ -155,14 +163,24 @@ __device__ __forceinline__ void store_scan_rows(const DevTable &t, uint32_t lane
     }
 }
 
-// the emit pass, a wave per leaf: each 64-slot group's emitting lanes rank themselves by ballot,
-// put their heap rows into the wave's LDS list by rank and write meta / status at their
-// positions; the leaf's records then leave as consecutive rows (store_scan_rows) or windows
-// (store_scan_windows), cut at max_records.  The counts of the leaf's tile, the tile's offset and
-// the head words are loaded together before any of them is used, then the slot words of the
-// lanes the head names: two round trips to the heap-row loads instead of four dependent ones.
-template <bool VIS, bool WIN>
-__global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, TableScanArgs g) {
+// the emit pass of both families, a wave per leaf.
+// Shared: the counts of the leaf's tile, the tile's offset and the first head or mask word are
+// loaded together before any of them is used, then the slot words of the lanes they name (two
+// round trips to the heap-row loads instead of four dependent ones); the leaf's first position;
+// each 64-slot group's emitting lanes rank themselves, put their heap rows into the wave's LDS
+// list by rank and write meta / status at their positions; the leaf's records then leave as
+// consecutive rows (store_scan_rows) or windows (store_scan_windows), cut at max_records.
+// Different, chosen at compile time by Args::matched (SEL below) -- where the emitting lanes come
+// from:
+//   every slot (TableScanArgs): the lanes the head names (snapshot) or the lanes below the record
+//     count whose meta word is non-zero (raw); the emitting lanes are a ballot over them.
+//   the match pass's bits (TableScanMatchArgs): the stored word is the ballot; a leaf without a
+//     match is skipped after its offset is written, a group without one costs its mask word; the
+//     matched lanes resolve image and status again (the same image: the passes are stream-ordered
+//     on one published image); row_slot is written.
+template <bool VIS, bool WIN, class Args>
+__global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, Args g) {
+    constexpr bool SEL = Args::matched;
     __shared__ uint32_t s_img[4][kTableScanMaxCap];
     const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
     uint32_t *rk = s_img[wv];
@@ -173,25 +191,42 @@ __global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, TableS
         const uint32_t leaf = g.leaf0 + (uint32_t)i;
         const uint64_t base = (uint64_t)leaf * t.cap;
         const uint64_t tile = i >> 6;
-        uint32_t v = lane < (uint32_t)(i & 63u) ? g.cnt[tile * 64 + lane] : 0u;
+        const uint32_t self = (uint32_t)(i & 63u);
+        // the counts of the tile's earlier leaves; SEL: one lane more, the leaf's own count
+        uint32_t v = lane < (SEL ? self + 1u : self) ? g.cnt[tile * 64 + lane] : 0u;
         const uint64_t tile0 = g.toff[tile];
-        uint32_t rc = t.cap;
-        if (!VIS)
-            rc = *reinterpret_cast<const uint32_t *>(t.head + (uint64_t)leaf * t.head_bytes +
-                                                     head_info_offset(t.cap, t.key_words)) & 0xFFFFu;
-        uint64_t vm = VIS ? head_vis(t, leaf, 0) : 0ull;
+        uint32_t rc = t.cap;  // raw unfiltered scan: the head's record count; otherwise every group is visited
+        uint32_t own = 1;     // SEL: the leaf's matches, 0 skips the leaf; the unfiltered scan never skips one here
+        uint64_t vm = 0;      // the group's head word (VIS) or mask word (SEL); unused in the raw unfiltered scan
+        if constexpr (SEL) {
+            vm = uni64(g.mask[i * spl]);
+            own = rl32(v, (int)self);
+            v = lane < self ? v : 0u;
+        } else {
+            if (!VIS)
+                rc = *reinterpret_cast<const uint32_t *>(t.head + (uint64_t)leaf * t.head_bytes +
+                                                         head_info_offset(t.cap, t.key_words)) & 0xFFFFu;
+            if (VIS) vm = head_vis(t, leaf, 0);
+        }
         // the leaf's first position: its tile's offset and the tile's earlier leaves
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
         const uint64_t pos0 = tile0 + uni32(v);
         if (g.leaf_offsets && lane == 0) g.leaf_offsets[i] = pos0;
-        if (pos0 >= g.max_records) continue;
-        rc = uni32(rc);
-        if (rc > t.cap) rc = t.cap;
+        if (own == 0 || pos0 >= g.max_records) continue;
+        if constexpr (!SEL) {
+            rc = uni32(rc);
+            if (rc > t.cap) rc = t.cap;
+        }
         uint32_t produced = 0;
-        for (uint32_t s = 0; s < spl && s * 64u < rc; ++s) {
-            if (VIS && s) vm = head_vis(t, leaf, (int)s);
-            bool on = VIS ? ((vm >> lane) & 1) != 0 : s * 64u + lane < rc;
+        for (uint32_t s = 0; s < spl && (SEL || s * 64u < rc); ++s) {
+            if constexpr (SEL) {
+                if (s) vm = uni64(g.mask[i * spl + s]);
+                if (vm == 0) continue;
+            } else if (VIS && s) {
+                vm = head_vis(t, leaf, (int)s);
+            }
+            bool on = VIS || SEL ? ((vm >> lane) & 1) != 0 : s * 64u + lane < rc;
             uint64_t meta = 0;
             uint32_t img = 0xFFFFFFFFu;
             uint8_t st = ST_LATEST;
@@ -202,10 +237,10 @@ __global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, TableS
                     img = scan_visible(t, si, g.rid, st);
                 } else {
                     img = si.image;
-                    on = meta != 0;  // 0: a deleted slot
+                    if (!SEL) on = meta != 0;  // 0: a deleted slot
                 }
             }
-            const uint64_t em = ballot(on);
+            const uint64_t em = SEL ? vm : ballot(on);
             if (on) {
                 const uint32_t r = produced + count_below(em);  // < cap
                 rk[r] = img;
@@ -213,6 +248,8 @@ __global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, TableS
                 if (k < g.max_records) {
                     if (g.row_meta) g.row_meta[k] = meta;
                     if (g.row_status) g.row_status[k] = st;
+                    if constexpr (SEL)
+                        if (g.row_slot) g.row_slot[k] = ((uint64_t)leaf << 16) | (s * 64u + lane);
                 }
             }
             produced += (uint32_t)__builtin_popcountll(em);
@@ -228,54 +265,14 @@ __global__ __launch_bounds__(256) void table_scan_emit_kernel(DevTable t, TableS
     }
 }
 
-uint64_t table_scan_scratch_bytes(uint64_t nl) { return ((nl + 63) / 64) * 8 + nl * 4; }
-
-hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
-                             uint32_t row_off, uint32_t len, uint32_t key_pad, const TableScanOut &o, uint8_t *scratch,
-                             hipStream_t s, const ScanTuning &tune) {
-    const bool win = len != 0;
-    // the leaves exist, a leaf's records fit the emit pass's list, and the window and the key lie
-    // inside a heap row (window_piece's and the key writer's loads rest on it)
-    if ((uint64_t)leaf0 + nl > t.nleaves || t.cap > kTableScanMaxCap || !o.count) return hipErrorInvalidValue;
-    if (win && ((uint64_t)row_off + len > t.hstride || key_pad > t.hstride || (key_pad & 7u))) return hipErrorInvalidValue;
-    if (o.max_records && !(win ? o.win : o.recs)) return hipErrorInvalidValue;
-    if (nl == 0) {
-        hipError_t e = hipMemsetAsync(o.count, 0, sizeof(uint64_t), s);
-        if (e == hipSuccess && o.leaf_offsets) e = hipMemsetAsync(o.leaf_offsets, 0, sizeof(uint64_t), s);
-        return e;
-    }
-    if (!scratch) return hipErrorInvalidValue;
-    const uint64_t ntiles = ((uint64_t)nl + 63) / 64;
-    uint64_t *toff = reinterpret_cast<uint64_t *>(scratch);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(scratch + ntiles * 8);
-    const int mb = max_blocks(tune);
-    if (snapshot) table_scan_count_kernel<true><<<grid_for(ntiles, 4, mb), 256, 0, s>>>(t, leaf0, nl, cnt, toff);
-    else table_scan_count_kernel<false><<<grid_for(ntiles, 4, mb), 256, 0, s>>>(t, leaf0, nl, cnt, toff);
-    table_scan_offsets_kernel<<<1, 1024, 0, s>>>(toff, ntiles, o.count, o.leaf_offsets ? o.leaf_offsets + nl : nullptr);
-    if (o.max_records || o.leaf_offsets) {
-        const TableScanArgs g{leaf0, nl, cnt, toff, o.max_records, o.leaf_offsets, o.row_meta, o.row_status, o.recs,
-                              ScanWindowArgs{WindowArgs{row_off, len, (len + 15u) >> 4, o.win}, o.row_keys, key_pad}, rid};
-        const int blocks = grid_for(nl, 4, mb);
-        if (snapshot) {
-            if (win) table_scan_emit_kernel<true, true><<<blocks, 256, 0, s>>>(t, g);
-            else table_scan_emit_kernel<true, false><<<blocks, 256, 0, s>>>(t, g);
-        } else {
-            if (win) table_scan_emit_kernel<false, true><<<blocks, 256, 0, s>>>(t, g);
-            else table_scan_emit_kernel<false, false><<<blocks, 256, 0, s>>>(t, g);
-        }
-    }
-    return hipGetLastError();
-}
-
 // ----------------------------------------------------------------------------------------
 // filtered whole-table scans (stage_table_scan_where / _where_window / _aggregate): the records
 // of the unfiltered scan that yield a tuple and on whose row bytes every predicate holds --
 // the per-tuple predicate of TableScanExecutor / IndexScanExecutor (executor.h:346-361, 465-534,
-// 573-642) evaluated on the device.  The same three stream-ordered steps: a match pass that
-// stores one bit per slot and the matches per leaf, the offsets of the tile sums
-// (table_scan_offsets_kernel, as it is), and an emit pass whose emitting lanes are the stored
-// bits.  The aggregate runs the match pass's loop alone and keeps count / sum / min / max in
-// registers.  Integer arithmetic only, no atomics, no workgroup waits for another.
+// 573-642) evaluated on the device.  A match pass stores one bit per slot and the matches per
+// leaf; the offsets and the emit pass above do the rest (TableScanMatchArgs).  The aggregate runs
+// the match pass's loop alone and keeps count / sum / min / max in registers.  Integer arithmetic
+// only, no atomics, no workgroup waits for another.
 
 // column `width` bytes at row byte src of heap row img, little-endian at any alignment, zero-
 // extended: out of the one or two aligned 8-B words that hold it.  The second word is read only
@@ -305,7 +302,7 @@ __device__ __forceinline__ bool preds_hold(const DevTable &t, uint32_t img, cons
         if (k < p.n) {
             const ScanPred &q = p.p[k];
             const uint64_t x = column_key(column_bits(t, img, q.src, q.width), q.width, q.is_signed != 0);
-            // lo / hi arrive in the same order domain (launch_table_scan_where flips a signed column's)
+            // lo / hi arrive in the same order domain (order_domain flips a signed column's)
             const bool in = x >= (uint64_t)q.lo && x <= (uint64_t)q.hi;
             ok &= in != (q.negate != 0);
         }
@@ -377,74 +374,6 @@ __global__ __launch_bounds__(256) void table_scan_tile_sums_kernel(const uint32_
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
         if (lane == 0) tsum[k] = c;
-    }
-}
-
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
-
-// what a filtered emit launch carries beside the emit pass's arguments (wave-uniform)
-struct TableScanWhereArgs {
-    TableScanArgs g;
-    const uint64_t *mask;  // [nl * cap / 64] the match pass's bits
-    uint64_t *row_slot;    // optional: (leaf << 16) | slot per record
-};
-
-// table_scan_emit_kernel with the emitting lanes taken from the match pass's bits: the matched
-// lanes read their slot word again and resolve image and status again (the same image: the
-// passes are stream-ordered on one published image), rank themselves, and the leaf's matches
-// leave through the same store paths.  A leaf without a match costs its mask words.
-template <bool VIS, bool WIN>
-__global__ __launch_bounds__(256) void table_scan_emit_where_kernel(DevTable t, TableScanWhereArgs a) {
-    __shared__ uint32_t s_img[4][kTableScanMaxCap];
-    const TableScanArgs &g = a.g;
-    const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
-    uint32_t *rk = s_img[wv];
-    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
-    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    const uint32_t spl = t.cap >> 6;
-    for (uint64_t i = wave; i < g.nl; i += nwaves) {
-        const uint32_t leaf = g.leaf0 + (uint32_t)i;
-        const uint64_t base = (uint64_t)leaf * t.cap;
-        const uint64_t tile = i >> 6;
-        const uint32_t self = (uint32_t)(i & 63u);
-        const uint32_t c = lane <= self ? g.cnt[tile * 64 + lane] : 0u;
-        const uint64_t tile0 = g.toff[tile];
-        uint64_t mk = uni64(a.mask[i * spl]);
-        const uint32_t own = rl32(c, (int)self);
-        uint32_t v = lane < self ? c : 0u;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-        const uint64_t pos0 = tile0 + uni32(v);
-        if (g.leaf_offsets && lane == 0) g.leaf_offsets[i] = pos0;
-        if (own == 0 || pos0 >= g.max_records) continue;
-        uint32_t produced = 0;
-        for (uint32_t s = 0; s < spl; ++s) {
-            if (s) mk = uni64(a.mask[i * spl + s]);
-            if (mk == 0) continue;
-            const bool on = ((mk >> lane) & 1) != 0;
-            if (on) {
-                const SlotInfo si = t.slot[base + s * 64u + lane];
-                uint8_t st = ST_LATEST;
-                const uint32_t img = VIS ? scan_visible(t, si, g.rid, st) : si.image;
-                const uint32_t r = produced + count_below(mk);  // < cap
-                rk[r] = img;
-                const uint64_t k = pos0 + r;
-                if (k < g.max_records) {
-                    if (g.row_meta) g.row_meta[k] = si.meta;
-                    if (g.row_status) g.row_status[k] = st;
-                    if (a.row_slot) a.row_slot[k] = ((uint64_t)leaf << 16) | (s * 64u + lane);
-                }
-            }
-            produced += (uint32_t)__builtin_popcountll(mk);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint64_t room = g.max_records - pos0;
-        const uint32_t e = produced < room ? produced : (uint32_t)room;
-        if (WIN) store_scan_windows(t, lane, pos0, e, rk, g.a);
-        else store_scan_rows(t, lane, pos0, e, rk, g.recs);
-        __builtin_amdgcn_wave_barrier();  // the list is rewritten on the next leaf
     }
 }
 
@@ -551,27 +480,40 @@ static ScanPreds order_domain(ScanPreds p) {
     return p;
 }
 
+// an integer column of a heap row: column_bits' loads rest on it
+static bool column_fits(uint32_t width, uint32_t src, uint32_t hstride) {
+    return scan_column_width(width) && (uint64_t)src + width <= hstride;
+}
+
 static bool preds_fit(const DevTable &t, const ScanPreds &p) {
     if (p.n > kScanPredMax) return false;
-    for (uint32_t k = 0; k < p.n; ++k) {
-        const uint32_t w = p.p[k].width;
-        if ((w != 1 && w != 2 && w != 4 && w != 8) || (uint64_t)p.p[k].src + w > t.hstride) return false;
-    }
+    for (uint32_t k = 0; k < p.n; ++k)
+        if (!column_fits(p.p[k].width, p.p[k].src, t.hstride)) return false;
     return true;
 }
 
-uint64_t table_scan_where_scratch_bytes(uint64_t nl, uint32_t cap) {
-    return ((nl + 63) / 64) * 8 + nl * (cap / 64) * 8 + nl * 4;
+template <class Args>
+static void launch_table_scan_emit(const DevTable &t, const Args &g, bool snapshot, bool win, int blocks, hipStream_t s) {
+    if (snapshot) {
+        if (win) table_scan_emit_kernel<true, true><<<blocks, 256, 0, s>>>(t, g);
+        else table_scan_emit_kernel<true, false><<<blocks, 256, 0, s>>>(t, g);
+    } else {
+        if (win) table_scan_emit_kernel<false, true><<<blocks, 256, 0, s>>>(t, g);
+        else table_scan_emit_kernel<false, false><<<blocks, 256, 0, s>>>(t, g);
+    }
 }
 
-hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
-                                   const ScanPreds &preds, uint32_t row_off, uint32_t len, uint32_t key_pad,
-                                   const TableScanOut &o, uint64_t *row_slot, uint8_t *scratch, hipStream_t s,
-                                   const ScanTuning &tune) {
+// both scan launchers; preds null: the unfiltered scan.  scratch: the tile offsets, with preds one
+// mask word per 64 slots, the records per leaf.
+static hipError_t table_scan_launches(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                      const ScanPreds *preds, uint32_t row_off, uint32_t len, uint32_t key_pad,
+                                      const TableScanOut &o, uint64_t *row_slot, uint8_t *scratch, hipStream_t s,
+                                      const ScanTuning &tune) {
     const bool win = len != 0;
-    // launch_table_scan's conditions, and every predicate column inside a heap row (column_bits'
-    // loads rest on it)
-    if ((uint64_t)leaf0 + nl > t.nleaves || t.cap > kTableScanMaxCap || !o.count || !preds_fit(t, preds))
+    // the leaves exist, a leaf's records fit the emit pass's list, and the window, the key and
+    // every predicate column lie inside a heap row (window_piece's, the key writer's and
+    // column_bits' loads rest on it)
+    if ((uint64_t)leaf0 + nl > t.nleaves || t.cap > kTableScanMaxCap || !o.count || (preds && !preds_fit(t, *preds)))
         return hipErrorInvalidValue;
     if (win && ((uint64_t)row_off + len > t.hstride || key_pad > t.hstride || (key_pad & 7u))) return hipErrorInvalidValue;
     if (o.max_records && !(win ? o.win : o.recs)) return hipErrorInvalidValue;
@@ -584,28 +526,47 @@ hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t n
     const uint64_t ntiles = ((uint64_t)nl + 63) / 64;
     uint64_t *toff = reinterpret_cast<uint64_t *>(scratch);
     uint64_t *mask = toff + ntiles;
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(mask + (uint64_t)nl * (t.cap / 64));
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(preds ? mask + (uint64_t)nl * (t.cap / 64) : mask);
     const int mb = max_blocks(tune);
-    const int blocks = grid_for(nl, 4, mb);
-    const ScanPreds p = order_domain(preds);
-    if (snapshot) table_scan_match_kernel<true><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
-    else table_scan_match_kernel<false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
-    table_scan_tile_sums_kernel<<<grid_for(ntiles, 4, mb), 256, 0, s>>>(cnt, nl, toff);
+    const int blocks = grid_for(nl, 4, mb), tile_blocks = grid_for(ntiles, 4, mb);
+    // records per leaf and per tile: from the heads alone, or the match pass and its tile sums
+    if (preds) {
+        const ScanPreds p = order_domain(*preds);
+        if (snapshot) table_scan_match_kernel<true><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
+        else table_scan_match_kernel<false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, mask, cnt);
+        table_scan_tile_sums_kernel<<<tile_blocks, 256, 0, s>>>(cnt, nl, toff);
+    } else if (snapshot) {
+        table_scan_count_kernel<true><<<tile_blocks, 256, 0, s>>>(t, leaf0, nl, cnt, toff);
+    } else {
+        table_scan_count_kernel<false><<<tile_blocks, 256, 0, s>>>(t, leaf0, nl, cnt, toff);
+    }
     table_scan_offsets_kernel<<<1, 1024, 0, s>>>(toff, ntiles, o.count, o.leaf_offsets ? o.leaf_offsets + nl : nullptr);
     if (o.max_records || o.leaf_offsets) {
-        const TableScanWhereArgs a{
-            TableScanArgs{leaf0, nl, cnt, toff, o.max_records, o.leaf_offsets, o.row_meta, o.row_status, o.recs,
-                          ScanWindowArgs{WindowArgs{row_off, len, (len + 15u) >> 4, o.win}, o.row_keys, key_pad}, rid},
-            mask, row_slot};
-        if (snapshot) {
-            if (win) table_scan_emit_where_kernel<true, true><<<blocks, 256, 0, s>>>(t, a);
-            else table_scan_emit_where_kernel<true, false><<<blocks, 256, 0, s>>>(t, a);
-        } else {
-            if (win) table_scan_emit_where_kernel<false, true><<<blocks, 256, 0, s>>>(t, a);
-            else table_scan_emit_where_kernel<false, false><<<blocks, 256, 0, s>>>(t, a);
-        }
+        const TableScanArgs g{leaf0, nl, cnt, toff, o.max_records, o.leaf_offsets, o.row_meta, o.row_status, o.recs,
+                              ScanWindowArgs{WindowArgs{row_off, len, (len + 15u) >> 4, o.win}, o.row_keys, key_pad}, rid};
+        if (preds) launch_table_scan_emit(t, TableScanMatchArgs{g, mask, row_slot}, snapshot, win, blocks, s);
+        else launch_table_scan_emit(t, g, snapshot, win, blocks, s);
     }
     return hipGetLastError();
+}
+
+uint64_t table_scan_scratch_bytes(uint64_t nl) { return ((nl + 63) / 64) * 8 + nl * 4; }
+
+uint64_t table_scan_where_scratch_bytes(uint64_t nl, uint32_t cap) {
+    return table_scan_scratch_bytes(nl) + nl * (cap / 64) * 8;
+}
+
+hipError_t launch_table_scan(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                             uint32_t row_off, uint32_t len, uint32_t key_pad, const TableScanOut &o, uint8_t *scratch,
+                             hipStream_t s, const ScanTuning &tune) {
+    return table_scan_launches(t, leaf0, nl, snapshot, rid, nullptr, row_off, len, key_pad, o, nullptr, scratch, s, tune);
+}
+
+hipError_t launch_table_scan_where(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                   const ScanPreds &preds, uint32_t row_off, uint32_t len, uint32_t key_pad,
+                                   const TableScanOut &o, uint64_t *row_slot, uint8_t *scratch, hipStream_t s,
+                                   const ScanTuning &tune) {
+    return table_scan_launches(t, leaf0, nl, snapshot, rid, &preds, row_off, len, key_pad, o, row_slot, scratch, s, tune);
 }
 
 // the match pass's grid: a partial per block is 32 B of scratch, and a grid of a few blocks per
@@ -620,9 +581,7 @@ hipError_t launch_table_scan_aggregate(const DevTable &t, uint32_t leaf0, uint32
                                        const ScanPreds &preds, uint32_t agg_src, uint32_t agg_width, bool agg_signed,
                                        uint64_t *agg, uint8_t *scratch, hipStream_t s, const ScanTuning &tune) {
     if ((uint64_t)leaf0 + nl > t.nleaves || !agg || !preds_fit(t, preds)) return hipErrorInvalidValue;
-    if (agg_width && ((agg_width != 1 && agg_width != 2 && agg_width != 4 && agg_width != 8) ||
-                      (uint64_t)agg_src + agg_width > t.hstride))
-        return hipErrorInvalidValue;
+    if (agg_width && !column_fits(agg_width, agg_src, t.hstride)) return hipErrorInvalidValue;
     if (nl && !scratch) return hipErrorInvalidValue;
     const ScanAggCol col{agg_src, agg_width, agg_signed ? 1u : 0u};
     AggAcc *part = reinterpret_cast<AggAcc *>(scratch);

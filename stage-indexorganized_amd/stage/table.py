@@ -80,6 +80,17 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _dev(b):
+    """the pointer of a DeviceBuffer or Stream; a raw pointer or None as it is"""
+    return getattr(b, "ptr", b)
+
+
+def _scan_range(leaves, read_id):
+    """-> (leaf_begin, leaf_end, read_id boxed for the C call or None) of a table scan"""
+    begin, end = (0, LEAF_END) if leaves is None else leaves
+    return begin, end, ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+
+
 class DeviceBuffer:
     """A hipMalloc'd buffer owned by Python."""
 
@@ -768,10 +779,8 @@ class Table:
         mode; d_out takes max_records rows of `stride` bytes or windows of window_stride(len)
         bytes, d_leaf_offsets end - begin + 1 u64 words, d_row_keys key_pad bytes per record,
         d_row_meta one u64 and d_row_status one byte per record.  Enqueued on `stream`."""
-        def p(b):
-            return getattr(b, "ptr", b)
-        begin, end = (0, LEAF_END) if leaves is None else leaves
-        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        begin, end, rid = _scan_range(leaves, read_id)
+        p = _dev
         if window is None:
             check(lib().stage_table_scan(self.h, begin, end, rid, max_records, p(d_count), p(d_leaf_offsets), p(d_out),
                                          p(d_row_meta), p(d_row_status), p(stream)), "stage_table_scan")
@@ -779,6 +788,43 @@ class Table:
             check(lib().stage_table_scan_window(self.h, begin, end, rid, window[0], window[1], max_records, p(d_count),
                                                 p(d_leaf_offsets), p(d_out), p(d_row_keys), p(d_row_meta),
                                                 p(d_row_status), p(stream)), "stage_table_scan_window")
+
+    def _table_scan(self, filtered, leaves, read_id, preds, window, row_keys, row_meta, row_slot, max_records):
+        """table_scan and (filtered: preds and row_slot apply) table_scan_where on buffers sized here"""
+        if row_keys and window is None:
+            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
+        begin, end = (0, LEAF_END) if leaves is None else leaves
+
+        def scan(m, d_off=None, d_out=None, d_key=None, d_slot=None, d_meta=None, d_st=None):
+            if not filtered:
+                self.table_scan_device((begin, end), read_id, m, d_cnt, d_off, d_out, window, d_key, d_meta, d_st)
+            else:
+                self.table_scan_where_device((begin, end), read_id, preds, m, d_cnt, d_off, d_out, window, d_key, d_slot,
+                                             d_meta, d_st)
+            check(lib().stage_device_sync(), "sync")
+            return int(d_cnt.to_numpy(np.uint64, 1)[0])
+
+        d_cnt = DeviceBuffer(8)
+        # count first: a bad range, window or predicate, or a stale image, is the library's error,
+        # raised before any buffer is sized
+        count = scan(0)
+        if end == LEAF_END:
+            end = self.stats()["leaves"]
+        m = count if max_records is None else min(count, int(max_records))
+        width = self.stride if window is None else window_stride(window[1])
+        d_off = DeviceBuffer((end - begin + 1) * 8)
+        d_out = DeviceBuffer(max(1, m * width))
+        d_key = DeviceBuffer(max(1, m * self.key_pad)) if row_keys else None
+        d_slot = DeviceBuffer(max(1, m * 8)) if row_slot else None
+        d_meta = DeviceBuffer(max(1, m * 8)) if row_meta else None
+        d_st = DeviceBuffer(max(1, m))
+        res = TableScanResult(scan(m, d_off, d_out, d_key, d_slot, d_meta, d_st), d_off.to_numpy(np.uint64, end - begin + 1),
+                              d_out.to_numpy(np.uint8, m * width).reshape(m, width),
+                              d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
+                              d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m))
+        if not filtered:
+            return res
+        return TableScanWhereResult(*res, d_slot.to_numpy(np.uint64, m) if row_slot else None)
 
     def table_scan(self, leaves=None, read_id=None, window=None, row_keys=False, row_meta=False, max_records=None):
         """TableScanExecutor with scan_sz == -1: every record of the leaves [begin, end) (None: the
@@ -790,30 +836,7 @@ class Table:
         records = rows[m, stride] or, with window=(payload_off, len), win[m, window_stride(len)]
         for the m = min(count, max_records) delivered records, keys[m, key_pad] with
         row_keys=True (window form), meta[m] with row_meta=True, status[m]."""
-        if row_keys and window is None:
-            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
-        begin, end = (0, LEAF_END) if leaves is None else leaves
-        d_cnt = DeviceBuffer(8)
-        # count first: a bad range or window, or a stale image, is the library's error, raised
-        # before any buffer is sized
-        self.table_scan_device((begin, end), read_id, 0, d_cnt, window=window)
-        check(lib().stage_device_sync(), "sync")
-        count = int(d_cnt.to_numpy(np.uint64, 1)[0])
-        if end == LEAF_END:
-            end = self.stats()["leaves"]
-        m = count if max_records is None else min(count, int(max_records))
-        width = self.stride if window is None else window_stride(window[1])
-        d_off = DeviceBuffer((end - begin + 1) * 8)
-        d_out = DeviceBuffer(max(1, m * width))
-        d_key = DeviceBuffer(max(1, m * self.key_pad)) if row_keys else None
-        d_meta = DeviceBuffer(max(1, m * 8)) if row_meta else None
-        d_st = DeviceBuffer(max(1, m))
-        self.table_scan_device((begin, end), read_id, m, d_cnt, d_off, d_out, window, d_key, d_meta, d_st)
-        check(lib().stage_device_sync(), "sync")
-        return TableScanResult(int(d_cnt.to_numpy(np.uint64, 1)[0]), d_off.to_numpy(np.uint64, end - begin + 1),
-                               d_out.to_numpy(np.uint8, m * width).reshape(m, width),
-                               d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
-                               d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m))
+        return self._table_scan(False, leaves, read_id, None, window, row_keys, row_meta, False, max_records)
 
     def table_scan_where_device(self, leaves, read_id, preds, max_records, d_count, d_leaf_offsets=None, d_out=None,
                                 window=None, d_row_keys=None, d_row_slot=None, d_row_meta=None, d_row_status=None,
@@ -821,10 +844,8 @@ class Table:
         """stage_table_scan_where (window None) / stage_table_scan_where_window on device buffers:
         table_scan_device's arguments, preds = a sequence of Pred (at most 4, all must hold; empty:
         every record that yields a tuple), d_row_slot one u64 per record.  Enqueued on `stream`."""
-        def p(b):
-            return getattr(b, "ptr", b)
-        begin, end = (0, LEAF_END) if leaves is None else leaves
-        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        begin, end, rid = _scan_range(leaves, read_id)
+        p = _dev
         arr, n = _pack_preds(preds)
         if window is None:
             check(lib().stage_table_scan_where(self.h, begin, end, rid, arr, n, max_records, p(d_count),
@@ -842,40 +863,13 @@ class Table:
         holds, in the same order, compacted.  Returns TableScanWhereResult: table_scan's fields
         (count = the matches of the range, offsets = the position of each leaf's first match) and
         slots[m] = (leaf << 16) | slot with row_slot=True."""
-        if row_keys and window is None:
-            raise ValueError("row_keys belongs to the window form: the rows carry their keys")
-        begin, end = (0, LEAF_END) if leaves is None else leaves
-        d_cnt = DeviceBuffer(8)
-        self.table_scan_where_device((begin, end), read_id, preds, 0, d_cnt, window=window)
-        check(lib().stage_device_sync(), "sync")
-        count = int(d_cnt.to_numpy(np.uint64, 1)[0])
-        if end == LEAF_END:
-            end = self.stats()["leaves"]
-        m = count if max_records is None else min(count, int(max_records))
-        width = self.stride if window is None else window_stride(window[1])
-        d_off = DeviceBuffer((end - begin + 1) * 8)
-        d_out = DeviceBuffer(max(1, m * width))
-        d_key = DeviceBuffer(max(1, m * self.key_pad)) if row_keys else None
-        d_slot = DeviceBuffer(max(1, m * 8)) if row_slot else None
-        d_meta = DeviceBuffer(max(1, m * 8)) if row_meta else None
-        d_st = DeviceBuffer(max(1, m))
-        self.table_scan_where_device((begin, end), read_id, preds, m, d_cnt, d_off, d_out, window, d_key, d_slot,
-                                     d_meta, d_st)
-        check(lib().stage_device_sync(), "sync")
-        return TableScanWhereResult(
-            int(d_cnt.to_numpy(np.uint64, 1)[0]), d_off.to_numpy(np.uint64, end - begin + 1),
-            d_out.to_numpy(np.uint8, m * width).reshape(m, width),
-            d_key.to_numpy(np.uint8, m * self.key_pad).reshape(m, self.key_pad) if row_keys else None,
-            d_meta.to_numpy(np.uint64, m) if row_meta else None, d_st.to_numpy(np.uint8, m),
-            d_slot.to_numpy(np.uint64, m) if row_slot else None)
+        return self._table_scan(True, leaves, read_id, preds, window, row_keys, row_meta, row_slot, max_records)
 
     def table_scan_aggregate_device(self, leaves, read_id, preds, agg, d_agg, stream=None):
         """stage_table_scan_aggregate into d_agg (32 bytes of device memory: count, sum, min, max);
         agg = (payload_off, width, signed) or None for the count alone.  Enqueued on `stream`."""
-        def p(b):
-            return getattr(b, "ptr", b)
-        begin, end = (0, LEAF_END) if leaves is None else leaves
-        rid = ctypes.byref(ctypes.c_uint32(read_id)) if read_id is not None else None
+        begin, end, rid = _scan_range(leaves, read_id)
+        p = _dev
         arr, n = _pack_preds(preds)
         off, width, signed = (0, 0, False) if agg is None else agg
         check(lib().stage_table_scan_aggregate(self.h, begin, end, rid, arr, n, off, width, int(signed), p(d_agg),

@@ -18,7 +18,8 @@ import stage
 from stage import Pred
 from table_scan_expect import LAST, raw_expect, snapshot_expects
 from table_scan_where_expect import Filtered, aggregate, column, domain, match_mask, raw_slots, snapshot_slots
-from test_gpu_table_scan import END, FILL, GUARD, TABLES, Case, case, expect, modes, some_ranges  # noqa: F401
+from test_gpu_table_scan import (END, FILL, GUARD, TABLES, Case, case, device_scan, expect, modes,  # noqa: F401
+                                 some_ranges)
 from test_gpu_write_path import oracle_epoch
 
 pytestmark = pytest.mark.gpu
@@ -473,6 +474,101 @@ def test_filtered_is_the_unfiltered_scan_indexed_by_the_mask(wcase):
             assert got[0] == res.count and got[1] == sum(int(v) for v in x) % (1 << 64)
             if res.count:
                 assert got[2:] == (int(x.min()), int(x.max()))
+
+
+# ------------------------------------------------------------------------------------------
+# the emit loop both families share: groups and leaves without a match, a cut between two groups
+
+def group_matches(c, rid, mask):
+    """-> [leaf, 64-slot group]: the group holds a match, from the oracle's (leaf, slot) numbers"""
+    s = c.slots[rid][mask]
+    g = np.zeros((c.nl, c.tab.leaf_capacity // 64), bool)
+    g[(s >> np.uint64(16)).astype(np.int64), ((s & np.uint64(0xFFFF)) >> np.uint64(6)).astype(np.int64)] = True
+    return g
+
+
+def loop_paths(g):
+    """-> (a leaf whose first matching group lies behind a group without a match, a leaf without a
+    match between two leaves that have some, a leaf with matches in two or more groups); -1: none"""
+    has = g.any(axis=1)
+    some = np.nonzero(has)[0]
+    late = np.nonzero(has & (g.argmax(axis=1) > 0))[0]
+    empty = np.nonzero(~has[some[0]:some[-1]])[0] + some[0] if some.size else some
+    two = np.nonzero(g.sum(axis=1) >= 2)[0]
+    return tuple(int(x[0]) if x.size else -1 for x in (late, empty, two))
+
+
+def loop_interval(c, rid):
+    """an interval predicate on the primary column that takes every path of loop_paths: the k
+    smallest values as make_classes' "sparse" does, else k consecutive values of the sorted column
+    (the oracle's per-slot values), k as large as it can be"""
+    e = expect(c, rid)
+    off, width, signed = PRIMARY
+    x, live = column(e.rows, c.key_pad, *PRIMARY), e.status != stage.ST_NOT_FOUND
+    vals = np.sort(x[live])
+    for k in range(min(vals.size, 8 * c.nl), 2, -1):  # as many matches as still leave a leaf without one
+        for i in [0] + list(range(k, vals.size - k + 1, k)):
+            if min(loop_paths(group_matches(c, rid, live & (x >= vals[i]) & (x <= vals[i + k - 1])))) >= 0:
+                return [Pred(off, width, int(vals[i]), int(vals[i + k - 1]))]
+    raise AssertionError((c.name, rid, "no interval of the primary column takes every path"))
+
+
+@pytest.mark.parametrize("case", ["key8_large_leaves", "key16", "key32"], indirect=True)
+def test_groups_and_leaves_without_a_match_and_a_cut_between_groups(wcase):
+    """a predicate under which a leaf's first groups hold no match, a whole leaf between two
+    matching ones holds none, and a leaf's matches span two groups -- asserted on the oracle --
+    then rows and one window, raw and one snapshot mode, every optional output, whole and cut
+    inside the leaf whose matches span two groups: the device's unfiltered scan indexed by the
+    numpy mask, and nothing past the cut"""
+    c = wcase
+    assert c.tab.leaf_capacity >= 512, (c.name, c.tab.leaf_capacity)  # eight or more 64-slot groups per leaf
+    window = c.windows[0]
+    for rid in (None, c.rids[1]):
+        preds = loop_interval(c, rid)
+        f = filtered(c, rid, preds)
+        g = group_matches(c, rid, f.mask)
+        late, empty, two = loop_paths(g)
+        what = (c.name, rid, preds)
+        assert g.shape[1] >= 8 and g[late].any() and not g[late, 0], what
+        assert not g[empty].any() and g[:empty].any() and g[empty + 1:].any(), what
+        assert g[two].sum() >= 2, what
+        # the cut: behind the matches of the leaf's first matching group, before those of its next
+        in_group = (f.slots >> np.uint64(16) == two) & ((f.slots & np.uint64(0xFFFF)) >> np.uint64(6) == g[two].argmax())
+        cut = int(f.offsets[two]) + int(in_group.sum())
+        total = int(f.offsets[-1])
+        assert f.offsets[two] < cut < f.offsets[two + 1] <= total, what
+
+        rows = device_scan(c, 0, c.nl, rid)
+        n = expect(c, rid).meta.size
+        un = {"rows": rows["out"][:n * c.stride].reshape(n, c.stride), "meta": rows["meta"][:n * 8].view(np.uint64),
+              "status": rows["status"][:n], "offsets": rows["offsets"][:(c.nl + 1) * 8].view(np.uint64)}
+        mask = un["status"] != stage.ST_NOT_FOUND
+        x = column(un["rows"], c.key_pad, *PRIMARY)
+        mask &= (x >= np.uint64(preds[0].lo)) & (x <= np.uint64(preds[0].hi))
+        assert np.array_equal(mask, f.mask), what
+        leaf_of = np.repeat(np.arange(c.nl), np.diff(un["offsets"].astype(np.int64)))
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(leaf_of[mask], minlength=c.nl))]).astype(np.uint64)
+        win = device_scan(c, 0, c.nl, rid, window=window)
+        ws = win["width"]
+        un["win"] = win["out"][:n * ws].reshape(n, ws)
+        un["keys"] = win["keys"][:n * c.key_pad].reshape(n, c.key_pad)
+
+        for m in (None, cut):
+            k = total if m is None else m
+            for w in (None, window):
+                got = device_where(c, 0, c.nl, rid, preds, window=w, max_records=m, room=total)
+                assert got["count"][:8].view(np.uint64)[0] == total and (got["count"][8:] == FILL).all(), (what, m, w)
+                assert np.array_equal(got["offsets"][:(c.nl + 1) * 8].view(np.uint64), offsets), (what, m, w)
+                assert (got["offsets"][(c.nl + 1) * 8:] == FILL).all(), (what, m, w)
+                exp = {"out": un["rows" if w is None else "win"][mask][:k], "meta": un["meta"][mask][:k],
+                       "status": un["status"][mask][:k], "slot": c.slots[rid][mask][:k]}
+                if w is not None:
+                    exp["keys"] = un["keys"][mask][:k]
+                for name, want in exp.items():
+                    nb = np.ascontiguousarray(want).view(np.uint8).reshape(-1)
+                    assert np.array_equal(got[name][:nb.size], nb), (what, m, w, name)
+                    assert (got[name][nb.size:] == FILL).all(), (what, m, w, name)  # past the cut, and the guard
+                assert np.array_equal(exp["slot"] >> np.uint64(16), leaf_of[mask][:k].astype(np.uint64)), (what, m, w)
 
 
 # ------------------------------------------------------------------------------------------
