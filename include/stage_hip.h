@@ -534,8 +534,8 @@ typedef struct stage_scan_agg {    /* 32 B, device memory */
  *   and order-free, so bit-exact whatever the grid.  No record output.  Errors as above, for the
  *   predicates and for the aggregate column (agg_signed above 1 too), and null d_agg.  An empty
  *   range gives count 0 and the identities.  Scratch: one 32-B partial per workgroup.
- *   Not covered: group-by, byte-string and LIKE predicates, disjunctions, predicates on key
- *   bytes, host-buffer and sharded forms. */
+ *   Not covered: byte-string and LIKE predicates, disjunctions, predicates on key bytes,
+ *   host-buffer and sharded forms.  Aggregates per group: stage_table_scan_group_aggregate below. */
 int stage_table_scan_where(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
                            const uint32_t *read_id,          /* host pointer; NULL = raw */
                            const stage_scan_pred *preds,     /* host pointer */
@@ -552,6 +552,68 @@ int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t lea
                                const uint32_t *read_id, const stage_scan_pred *preds,
                                uint32_t n_pred, uint32_t agg_off, uint32_t agg_width /* 0 = count only */,
                                uint32_t agg_signed, stage_scan_agg *d_agg, void *stream);
+/* stage_table_scan_group_aggregate (executor.h:346-361, 465-534, 573-642): GROUP BY one integer
+ *   column -- stage_table_scan_aggregate's count / sum / min / max per value of a group column, in
+ *   one pass, as the per-group MIN(s_quantity) ... GROUP BY s_i_id of RunQuery2's SQL
+ *   (tpcc_new_order.cpp:621-630) or CH-benCHmark Q1's groups by ol_number, a field of ORDER_LINE's
+ *   32-byte key.  group is a HOST pointer, read during the call; d_groups is device memory of
+ *   n_groups + 1 stage_scan_agg records.
+ *   Record set: exactly stage_table_scan_aggregate's for the same range, mode (raw, or snapshot at
+ *   *read_id) and predicates; a record with no tuple never takes part.  The group column and the
+ *   aggregate column are read from the row bytes the row form writes for the record (the leaf
+ *   image for LATEST, the version's image for OLD, the current image in raw mode): the group column
+ *   at row byte key_pad + off, or with in_key at row byte off inside the row's first key_pad bytes;
+ *   the aggregate column (agg_off, agg_width, agg_signed) as in stage_table_scan_aggregate.
+ *   Group membership: with x the record's extended group value, the record belongs to group g iff
+ *   x == base + g in the mathematical integers, 0 <= g < n_groups.  Nothing wraps: an unsigned
+ *   8-byte column with base = 2^64 - 3 has three reachable groups, a signed column with base = -3
+ *   and 8 groups covers -3 .. 4.  Every other matching record belongs to the rest group, index
+ *   n_groups.
+ *   d_groups[g] = count, sum (modulo 2^64), min and max of the aggregate column over group g in
+ *   stage_scan_agg's conventions; a group with no record: count 0, sum 0, min = the aggregate
+ *   domain's largest value, max = its smallest; agg_width == 0: the counts alone, sum = min = max
+ *   = 0 everywhere.  An empty leaf range fills all n_groups + 1 records with these identities.
+ *   Nothing past (n_groups + 1) * 32 bytes is touched.  Folding the n_groups + 1 records (counts
+ *   and sums added, min of the mins, max of the maxes) gives exactly stage_table_scan_aggregate's
+ *   record for the same arguments.  Integer and order-free: bit-exact whatever the grid
+ *   (stage_set_scan_tuning's cap applies) and whichever of the two forms runs -- up to
+ *   STAGE_GROUP_LDS_MAX groups each workgroup aggregates in a table in LDS, and a second launch
+ *   folds the workgroups' tables; above that the records are added to d_groups directly; both
+ *   with 64-bit integer atomics.
+ *   STAGE_E_ARG, checked before the table's "needs stage_sync" state, in this order: the predicate
+ *   errors above; null group; the group column -- is_signed or in_key above 1, pad or pad2 != 0,
+ *   a width outside {1, 2, 4, 8}, off + width > payload_size (with in_key: > key_pad); n_groups 0
+ *   or above STAGE_GROUP_MAX; the aggregate column's errors; leaf_begin > leaf_end; null d_groups.
+ *   Then STAGE_E_STATE for a stale image, then the leaf-count check.
+ *   Per call the table's scratch holds 32 (n_groups + 1) W bytes for n_groups <=
+ *   STAGE_GROUP_LDS_MAX, one table per workgroup, W = min(ceil(nl / 4), the grid cap,
+ *   floor(2^26 / (32 (n_groups + 1)))) workgroups for nl leaves -- at most 64 MiB -- until the
+ *   work enqueued on `stream` ends (two launches); above STAGE_GROUP_LDS_MAX no scratch: d_groups
+ *   itself holds intermediate values until then (three launches).  One launch for an empty range.
+ *   Not covered: several aggregate columns in one pass, composite or hashed group keys,
+ *   byte-string groups, host-buffer and sharded forms, predicates on key bytes (only the group
+ *   column may be a key field). */
+#define STAGE_GROUP_MAX      (1u << 24)   /* largest n_groups */
+#define STAGE_GROUP_LDS_MAX  256u         /* largest n_groups the LDS form takes */
+typedef struct stage_scan_group {   /* 24 B, host memory, read during the call */
+    uint32_t off;        /* in_key 0: first payload byte of the column ((off, len) convention of
+                            stage_update); in_key 1: byte of the row's key field, off + width <= key_pad */
+    uint8_t  width;      /* 1, 2, 4 or 8 bytes, little-endian, at any alignment                  */
+    uint8_t  is_signed;  /* extension rule of stage_scan_pred                                    */
+    uint8_t  in_key;     /* 0 or 1                                                               */
+    uint8_t  pad;        /* 0                                                                    */
+    int64_t  base;       /* group 0's value, in the column's domain (unsigned column: the uint64
+                            bit pattern)                                                         */
+    uint32_t n_groups;   /* 1 .. STAGE_GROUP_MAX                                                 */
+    uint32_t pad2;       /* 0                                                                    */
+} stage_scan_group;
+int stage_table_scan_group_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end,
+                                     const uint32_t *read_id, const stage_scan_pred *preds,
+                                     uint32_t n_pred, const stage_scan_group *group /* host pointer */,
+                                     uint32_t agg_off, uint32_t agg_width /* 0 = counts only */,
+                                     uint32_t agg_signed,
+                                     stage_scan_agg *d_groups /* n_groups + 1 records, device */,
+                                     void *stream);
 /* The IndexScanExecutor range branch of stage_index_scan_batch consumed only up to its first
  * produced tuple (LATEST or OLD) whose key begins with the start key's first `prefix_words`
  * 8-byte fields (0..key_words) -- the predicate TPC-C stock-level puts on its ORDER_LINE scans
@@ -617,6 +679,13 @@ int stage_set_probe_tuning(stage_table *t, int group, int max_blocks);
  * launches -- stage_scan_batch, stage_index_scan_batch, their window forms and the first-tuple
  * scans; a capped grid strides over the batch.  A tuning knob, not a semantic one. */
 int stage_set_scan_tuning(stage_table *t, int max_blocks);
+/* stage_table_scan_group_aggregate's two choices, for measurements and tests; neither changes a
+ * bit of the result.  lds_max: the largest n_groups the LDS form takes, 0 .. STAGE_GROUP_LDS_MAX
+ * (0: the global form always), -1 = STAGE_GROUP_LDS_MAX.  combine: how many distinct groups among
+ * a wave's 64 records are reduced inside the wave before their entry is updated, 0 .. 64 (0: every
+ * record updates its entry itself), -1 = the default (none in the LDS form, the first lane's
+ * group in the global form). */
+int stage_set_scan_group_tuning(stage_table *t, int lds_max, int combine);
 
 /* cache policy of stage_probe_batch's output stores (rows + status records), 8-probe launch
  * shape: STAGE_STORE_TEMPORAL, STAGE_STORE_NONTEMPORAL (default) or STAGE_STORE_WRITE_THROUGH

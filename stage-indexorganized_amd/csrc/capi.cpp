@@ -660,12 +660,18 @@ int stage_index_scan_batch_window(stage_table *t, const uint64_t *d_start_keys, 
 }
 
 static_assert(sizeof(stage_scan_pred) == 24 && sizeof(stage_scan_agg) == 32, "stage_hip.h layout");
+static_assert(sizeof(stage_scan_group) == 24, "stage_hip.h layout");
 static_assert(STAGE_PRED_MAX == stage::kScanPredMax, "stage_hip.h mirrors kernel_api.hpp");
+static_assert(STAGE_GROUP_MAX == stage::kGroupMax && STAGE_GROUP_LDS_MAX == stage::kGroupLdsMax,
+              "stage_hip.h mirrors kernel_api.hpp");
 
-// one integer column (payload_off, width) against the table's parameters alone
-static int check_column(stage_table *t, const char *what, uint32_t payload_off, uint32_t width) {
+// one integer column (payload_off, width) against the table's parameters alone; in_key: the
+// column is a field of the row's key, `payload_off` a byte of the row's first key_pad bytes
+static int check_column(stage_table *t, const char *what, uint32_t payload_off, uint32_t width, bool in_key = false) {
     if (!stage::scan_column_width(width)) return fail(STAGE_E_ARG, std::string(what) + ": width must be 1, 2, 4 or 8");
-    if ((uint64_t)payload_off + width > facts(t).params().payload_size)
+    if (in_key && (uint64_t)payload_off + width > facts(t).key_pad())
+        return fail(STAGE_E_ARG, std::string(what) + ": off + width exceeds the table's padded key");
+    if (!in_key && (uint64_t)payload_off + width > facts(t).params().payload_size)
         return fail(STAGE_E_ARG, std::string(what) + ": payload_off + width exceeds the table's payload_size");
     return STAGE_OK;
 }
@@ -709,6 +715,8 @@ struct TableScanRequest {
     const stage_scan_pred *preds;
     uint32_t n_pred;
     const TableScanAggColumn *agg;  // null: the scan delivers records
+    bool grouped;                   // the grouped aggregate: group is checked
+    const stage_scan_group *group;
     const TableScanWindow *window;  // null: rows
     const void *d_result;           // d_count, or d_agg with an aggregate column
     uint64_t max_records;           // records: a record buffer must come with max_records != 0
@@ -720,21 +728,34 @@ using TableScanLaunch = std::function<hipError_t(uint32_t, uint32_t, bool, uint3
 
 // Every whole-table scan entry point (TableScanExecutor, executor.h:573-642; per record
 // IndexScanExecutor's rule, executor.h:465-534; the per-tuple predicate of executor.h:346-361):
-// the argument checks in one order -- predicates, aggregate column, window, leaf range, result
-// word, record buffer -- then, on the published image and the table's device, the launch.
+// the argument checks in one order -- predicates, group column, aggregate column, window, leaf
+// range, result word, record buffer -- then, on the published image and the table's device, the
+// launch.
 static int table_scan_call(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
                            const TableScanRequest &q, const TableScanLaunch &launch) {
     if (!t) return fail(STAGE_E_ARG, "null table");
     stage::ScanPreds p{};
     int rc = q.filtered ? check_preds(t, q.preds, q.n_pred, p) : STAGE_OK;
     if (rc) return rc;
+    if (q.grouped) {
+        const stage_scan_group *g = q.group;
+        if (!g) return fail(STAGE_E_ARG, "group column: null group");
+        if (g->is_signed > 1 || g->in_key > 1) return fail(STAGE_E_ARG, "group column: is_signed and in_key are 0 or 1");
+        if (g->pad != 0 || g->pad2 != 0) return fail(STAGE_E_ARG, "group column: pad and pad2 must be 0");
+        rc = check_column(t, "group column", g->off, g->width, g->in_key != 0);
+        if (rc) return rc;
+        if (g->n_groups == 0 || g->n_groups > STAGE_GROUP_MAX)
+            return fail(STAGE_E_ARG, "group column: n_groups must be 1 .. STAGE_GROUP_MAX");
+    }
     rc = q.agg && q.agg->width ? check_column(t, "aggregate column", q.agg->payload_off, q.agg->width) : STAGE_OK;
     if (rc) return rc;
     if (q.agg && q.agg->is_signed > 1) return fail(STAGE_E_ARG, "aggregate column: agg_signed is 0 or 1");
     rc = q.window ? check_window(t, q.window->payload_off, q.window->len) : STAGE_OK;
     if (rc) return rc;
     if (leaf_begin > leaf_end) return fail(STAGE_E_ARG, "table scan: leaf_begin exceeds leaf_end");
-    if (!q.d_result) return fail(STAGE_E_ARG, q.agg ? "table scan: null d_agg" : "table scan: null d_count");
+    if (!q.d_result)
+        return fail(STAGE_E_ARG, q.grouped ? "table scan: null d_groups" : q.agg ? "table scan: null d_agg"
+                                                                                  : "table scan: null d_count");
     if (q.max_records && !q.d_out) return fail(STAGE_E_ARG, "table scan: null record buffer with max_records != 0");
     rc = need_synced(t);
     if (rc) return rc;
@@ -755,7 +776,7 @@ static int table_scan(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, co
                       uint64_t max_records, uint64_t *d_count, uint64_t *d_leaf_offsets, uint8_t *d_out,
                       uint8_t *d_row_keys, uint64_t *d_row_slot, uint64_t *d_row_meta, uint8_t *d_row_status,
                       void *stream) {
-    const TableScanRequest q{filtered, preds, n_pred, nullptr, window, d_count, max_records, d_out,
+    const TableScanRequest q{filtered, preds, n_pred, nullptr, false, nullptr, window, d_count, max_records, d_out,
                              filtered ? "filtered table scan kernels" : "table scan kernels"};
     return table_scan_call(t, leaf_begin, leaf_end, read_id, q,
                            [&](uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid, const stage::ScanPreds &p) {
@@ -811,7 +832,8 @@ int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t lea
                                const stage_scan_pred *preds, uint32_t n_pred, uint32_t agg_off, uint32_t agg_width,
                                uint32_t agg_signed, stage_scan_agg *d_agg, void *stream) {
     const TableScanAggColumn col{agg_off, agg_width, agg_signed};
-    const TableScanRequest q{true, preds, n_pred, &col, nullptr, d_agg, 0, nullptr, "table scan aggregate kernels"};
+    const TableScanRequest q{true, preds, n_pred, &col, false, nullptr, nullptr, d_agg, 0, nullptr,
+                             "table scan aggregate kernels"};
     return table_scan_call(t, leaf_begin, leaf_end, read_id, q,
                            [&](uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid, const stage::ScanPreds &p) {
         const uint64_t bytes = stage::table_scan_aggregate_scratch_bytes(nl, t->scan_tune);
@@ -819,6 +841,26 @@ int stage_table_scan_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t lea
         return stage::launch_table_scan_aggregate(t->dev.view, leaf0, nl, snapshot, rid, p, facts(t).key_pad() + agg_off,
                                                   agg_width, agg_signed != 0, reinterpret_cast<uint64_t *>(d_agg), scratch,
                                                   pick(t, stream), t->scan_tune);
+    });
+}
+
+int stage_table_scan_group_aggregate(stage_table *t, uint64_t leaf_begin, uint64_t leaf_end, const uint32_t *read_id,
+                                     const stage_scan_pred *preds, uint32_t n_pred, const stage_scan_group *group,
+                                     uint32_t agg_off, uint32_t agg_width, uint32_t agg_signed, stage_scan_agg *d_groups,
+                                     void *stream) {
+    const TableScanAggColumn col{agg_off, agg_width, agg_signed};
+    const TableScanRequest q{true, preds, n_pred, &col, true, group, nullptr, d_groups, 0, nullptr,
+                             "table scan group aggregate kernels"};
+    return table_scan_call(t, leaf_begin, leaf_end, read_id, q,
+                           [&](uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid, const stage::ScanPreds &p) {
+        const uint32_t kp = facts(t).key_pad();
+        const stage::ScanGroupSpec g{group->in_key ? group->off : kp + group->off, group->width, group->is_signed != 0,
+                                     (uint64_t)group->base, group->n_groups};
+        const uint64_t bytes = stage::table_scan_group_scratch_bytes(nl, g.n, t->scan_tune, t->group_tune);
+        uint8_t *scratch = bytes ? stage::scratch_bytes(t->dev, bytes) : nullptr;
+        return stage::launch_table_scan_group(t->dev.view, leaf0, nl, snapshot, rid, p, g, kp + agg_off, agg_width,
+                                              agg_signed != 0, reinterpret_cast<uint64_t *>(d_groups), scratch,
+                                              pick(t, stream), t->scan_tune, t->group_tune);
     });
 }
 
@@ -860,6 +902,14 @@ int stage_set_probe_tuning(stage_table *t, int group, int max_blocks) {
 int stage_set_scan_tuning(stage_table *t, int max_blocks) {
     if (!t || max_blocks < 0) return fail(STAGE_E_ARG, "bad tuning");
     t->scan_tune.max_blocks = max_blocks;
+    return STAGE_OK;
+}
+
+int stage_set_scan_group_tuning(stage_table *t, int lds_max, int combine) {
+    if (!t || lds_max < -1 || lds_max > (int)STAGE_GROUP_LDS_MAX || combine < -1 || combine > 64)
+        return fail(STAGE_E_ARG, "bad tuning");
+    t->group_tune.lds_max = lds_max;
+    t->group_tune.combine = combine;
     return STAGE_OK;
 }
 

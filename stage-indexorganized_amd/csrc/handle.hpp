@@ -59,6 +59,7 @@ struct stage_table {
     stage::DeviceImage dev;
     stage::ProbeTuning tune;
     stage::ScanTuning scan_tune;
+    stage::ScanGroupTuning group_tune;  // stage_set_scan_group_tuning
     uint32_t out_stride = 0;  // 0 = stride of the canonical row (stage_set_output_layout / STAGE_OUT_STRIDE)
     int status_bytes = 32;    // stage_probe_batch's status records: 32 or 16 (stage_set_output_layout)
     std::unique_ptr<stage::ShardComm> comm;

@@ -163,6 +163,34 @@ uint64_t table_scan_aggregate_scratch_bytes(uint64_t nl, const ScanTuning &tune)
 hipError_t launch_table_scan_aggregate(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
                                        const ScanPreds &preds, uint32_t agg_src, uint32_t agg_width, bool agg_signed,
                                        uint64_t *agg, uint8_t *scratch, hipStream_t s, const ScanTuning &tune);
+// launch_table_scan_aggregate per group: groups[4 g .. 4 g + 3] = the words of stage_scan_agg over
+// the matching records whose group column (grp.src, grp.width, grp.is_signed) holds grp.base + g,
+// g < grp.n, in the integers (nothing wraps); entry grp.n = every other matching record.  An entry
+// without a record holds count 0, sum 0 and the identities of launch_table_scan_aggregate.
+// grp.n <= the LDS tier's bound: a table per workgroup in LDS (32 (grp.n + 1) bytes of dynamic
+// shared memory), left in scratch and folded by a second launch; above: a fill, the scan with
+// global atomics straight on groups[], a finish launch.  Stream order, one launch for an empty
+// range.  scratch: table_scan_group_scratch_bytes(nl, grp.n, tune, gt) bytes (one table per
+// workgroup of the LDS tier, at most 64 MiB; 0 in the global tier), 8-B aligned.  Integer and
+// order-free: the same bytes from either tier and any grid.
+constexpr uint32_t kGroupMax = 1u << 24;   // STAGE_GROUP_MAX
+constexpr uint32_t kGroupLdsMax = 256;     // STAGE_GROUP_LDS_MAX
+struct ScanGroupSpec {
+    uint32_t src, width;  // the group column at row byte src (key bytes lie below the key pad)
+    bool is_signed;
+    uint64_t base;        // the column's domain (unsigned column: the uint64 bit pattern)
+    uint32_t n;           // 1 .. kGroupMax
+};
+struct ScanGroupTuning {
+    int lds_max = -1;  // groups the LDS tier takes: -1 = kGroupLdsMax, 0 = the global tier always
+    int combine = -1;  // distinct groups of a wave's 64 records combined before the update: -1 =
+                       // by tier (table_scan.hip), 0 = none, 64 = all
+};
+uint64_t table_scan_group_scratch_bytes(uint64_t nl, uint32_t n_groups, const ScanTuning &tune, const ScanGroupTuning &gt);
+hipError_t launch_table_scan_group(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                   const ScanPreds &preds, const ScanGroupSpec &grp, uint32_t agg_src, uint32_t agg_width,
+                                   bool agg_signed, uint64_t *groups, uint8_t *scratch, hipStream_t s,
+                                   const ScanTuning &tune, const ScanGroupTuning &gt);
 // two single scans (no read id) of two tables in one launch, the same records as launch_scan of
 // each (n = 1): 8-byte keys, leaves of the same size above 128 slots, 1..63 records each
 // (scan_pair_supported; otherwise hipErrorInvalidValue and nothing is launched)

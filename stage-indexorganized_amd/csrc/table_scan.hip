@@ -1,5 +1,6 @@
 // table_scan.hip -- gfx950 kernels of the whole-table scan and of its filtered forms (a count or a
-// match pass, the offsets, one emit pass for both) and of the aggregate, and their launchers.
+// match pass, the offsets, one emit pass for both), of the aggregate and of the grouped aggregate,
+// and their launchers.
 #include "kernel_api.hpp"
 #include "launch_util.hpp"
 #include "row_store.hpp"
@@ -592,6 +593,261 @@ hipError_t launch_table_scan_aggregate(const DevTable &t, uint32_t leaf0, uint32
         else table_scan_aggregate_kernel<false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, col, part);
     }
     table_scan_aggregate_fold_kernel<<<1, 256, 0, s>>>(part, (uint32_t)blocks, col, agg);
+    return hipGetLastError();
+}
+
+
+// ----------------------------------------------------------------------------------------
+// grouped aggregate (stage_table_scan_group_aggregate): the aggregate's record set and loop, each
+// matching record added to the entry of its group -- count / sum / min / max per value of one
+// integer column, GROUP BY on the device (the per-group MIN of RunQuery2's SQL,
+// tpcc_new_order.cpp:621-630; executor.h:346-361, 465-534, 573-642 for the record set).  The
+// entries are AggAcc records (order-domain min / max) updated with 64-bit integer atomics.
+//   LDS tier (at most kGroupLdsMax groups): a table per workgroup in LDS, every lane updates its
+//     entry; the workgroup leaves its table in scratch and a fold launch, a workgroup per entry,
+//     reduces the tables and writes the records in the column's domain -- the aggregate's two
+//     steps with a table in place of one partial.
+//   global tier: a fill launch writes the order-domain identities into groups[], the scan launch
+//     updates groups[] itself, a finish launch turns min / max into the column's domain.  Updates
+//     of one entry serialise in the L2 (about 11 ns each, measured), so the lanes of a wave that
+//     share the first lane's group are reduced by shuffles, a wave keeps that result in registers
+//     while the next 64 records give the same group, and a workgroup's waves merge what they
+//     still hold at the end: a group that takes most records (the rest group, typically) costs
+//     one update per workgroup, not one per record.
+// Integer atomics are order-free, so both tiers and every grid give the same bytes; no workgroup
+// waits for another.
+
+// the group column of a launch (wave-uniform)
+struct ScanGroupCol {
+    uint32_t src, width, is_signed;
+    uint32_t n;     // groups; entry n is the rest group
+    uint64_t base;  // group 0's value in the order domain of column_key
+    uint32_t kmax;  // distinct groups of a wave's 64 records that are combined before the update
+};
+
+// one entry takes cnt records with sum, min and max (col false: the count alone).  No value
+// returns, so these are ds_add / ds_min / ds_max _u64 and global_atomic_ add / umin / umax _x2.
+template <bool LDS>
+__device__ __forceinline__ void group_entry_add(AggAcc *e, const AggAcc &v, bool col) {
+    constexpr int scope = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
+    __hip_atomic_fetch_add(&e->count, v.count, __ATOMIC_RELAXED, scope);
+    if (col) {
+        __hip_atomic_fetch_add(&e->sum, v.sum, __ATOMIC_RELAXED, scope);
+        __hip_atomic_fetch_min(&e->min, v.min, __ATOMIC_RELAXED, scope);
+        __hip_atomic_fetch_max(&e->max, v.max, __ATOMIC_RELAXED, scope);
+    }
+}
+
+// what a wave of the global tier still holds for one group (wave-uniform); g == kNoGroup: nothing
+constexpr uint32_t kNoGroup = 0xFFFFFFFFu;
+struct GroupPending {
+    uint32_t g;
+    AggAcc a;
+};
+
+// the wave's 64 records (on: the lane has one, of group g with order-domain value x and summand
+// sv) enter the table.  Up to kmax times the first remaining lane's group is taken out when two
+// or more lanes hold it: they are reduced by shuffles into one update -- of the entry (LDS), or
+// of what the wave holds (global tier: merged when it is the same group, else what was held goes
+// to its entry first).  The lanes that remain update their entries themselves.  Called by every
+// lane of the wave.
+template <bool LDS>
+__device__ __forceinline__ void group_wave_add(AggAcc *tab, GroupPending &pend, bool on, uint32_t g, uint64_t x,
+                                               uint64_t sv, bool col, uint32_t kmax, uint32_t lane) {
+    uint64_t todo = ballot(on);
+    for (uint32_t it = 0; todo != 0 && it < kmax; ++it) {
+        const int l = __builtin_ctzll(todo);
+        const uint32_t g0 = rl32(g, l);
+        const bool peer = on && g == g0;
+        const uint64_t peers = ballot(peer);
+        todo &= ~peers;
+        const uint32_t np = (uint32_t)__builtin_popcountll(peers);
+        if (np < 2) continue;
+        AggAcc v{np, peer ? sv : 0ull, peer ? x : ~0ull, peer ? x : 0ull};
+        if (col) {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                v.sum += (uint64_t)__shfl_xor((unsigned long long)v.sum, o, 64);
+                const uint64_t a = (uint64_t)__shfl_xor((unsigned long long)v.min, o, 64);
+                const uint64_t b = (uint64_t)__shfl_xor((unsigned long long)v.max, o, 64);
+                v.min = a < v.min ? a : v.min;
+                v.max = b > v.max ? b : v.max;
+            }
+        }
+        if (LDS) {
+            if (lane == (uint32_t)l) group_entry_add<true>(tab + g0, v, col);
+        } else if (pend.g == g0) {
+            agg_add(pend.a, v);
+        } else {
+            if (pend.g != kNoGroup && lane == 0) group_entry_add<false>(tab + pend.g, pend.a, col);
+            pend.g = g0;
+            pend.a = v;
+        }
+        on = on && !peer;
+    }
+    if (on) group_entry_add<LDS>(tab + g, AggAcc{1, sv, x, x}, col);
+}
+
+// the aggregate's loop.  LDS: out = the scratch tables, gc.n + 1 entries per workgroup; the
+// workgroup's table is dynamic shared memory, initialised to the identities and copied out at
+// the end.  Global tier: out = groups[].
+template <bool VIS, bool LDS>
+__global__ __launch_bounds__(256) void table_scan_group_kernel(DevTable t, uint32_t leaf0, uint32_t nl, uint32_t rid,
+                                                               ScanPreds p, ScanGroupCol gc, ScanAggCol col,
+                                                               AggAcc *__restrict__ out) {
+    extern __shared__ AggAcc s_groups[];
+    AggAcc *tab = LDS ? s_groups : out;
+    if (LDS) {
+        for (uint32_t k = threadIdx.x; k <= gc.n; k += blockDim.x) s_groups[k] = AggAcc{0, 0, ~0ull, 0};
+        __syncthreads();
+    }
+    const uint32_t lane = lane_id(), wv = uni32(threadIdx.x >> 6);
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wv;
+    const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    const uint32_t spl = t.cap >> 6;
+    const bool agg = col.width != 0;
+    GroupPending pend{kNoGroup, AggAcc{0, 0, ~0ull, 0}};
+    for (uint64_t i = wave; i < nl; i += nwaves) {
+        const uint32_t leaf = leaf0 + (uint32_t)i;
+        const uint32_t rc = scan_record_count<VIS>(t, leaf);
+        for (uint32_t s = 0; s < spl && s * 64u < rc; ++s) {
+            const uint32_t img = scan_group_image<VIS>(t, leaf, s, lane, rc, rid);
+            const bool on = img != 0xFFFFFFFFu && preds_hold(t, img, p);
+            uint32_t g = gc.n;
+            uint64_t x = 0;
+            if (on) {
+                // x - base in the integers: both are in the order domain, where nothing wraps
+                const uint64_t k = column_key(column_bits(t, img, gc.src, gc.width), gc.width, gc.is_signed != 0);
+                if (k >= gc.base && k - gc.base < gc.n) g = (uint32_t)(k - gc.base);
+                if (agg) x = column_key(column_bits(t, img, col.src, col.width), col.width, col.is_signed != 0);
+            }
+            if (ballot(on) == 0) continue;
+            group_wave_add<LDS>(tab, pend, on, g, x, col.is_signed ? x ^ (1ull << 63) : x, agg, gc.kmax, lane);
+        }
+    }
+    if constexpr (LDS) {
+        __syncthreads();
+        AggAcc *mine = out + (uint64_t)blockIdx.x * ((uint64_t)gc.n + 1);
+        for (uint32_t k = threadIdx.x; k <= gc.n; k += blockDim.x) mine[k] = s_groups[k];
+    } else {
+        // what the waves still hold: equal groups merged, one update each
+        __shared__ GroupPending s_pend[4];
+        if (lane == 0) s_pend[wv] = pend;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t nw = blockDim.x >> 6;
+            for (uint32_t k = 0; k < nw; ++k) {
+                GroupPending a = s_pend[k];
+                if (a.g == kNoGroup) continue;
+                for (uint32_t j = k + 1; j < nw; ++j)
+                    if (s_pend[j].g == a.g) {
+                        agg_add(a.a, s_pend[j].a);
+                        s_pend[j].g = kNoGroup;
+                    }
+                group_entry_add<false>(out + a.g, a.a, agg);
+            }
+        }
+    }
+}
+
+// an entry's record in the column's domain; no record: the identities of
+// table_scan_aggregate_fold_kernel (min = the domain's largest value, max = its smallest)
+__device__ __forceinline__ AggAcc group_record(AggAcc a, const ScanAggCol &col) {
+    if (!col.width) {
+        a.sum = a.min = a.max = 0;
+    } else if (a.count) {
+        const uint64_t flip = col.is_signed ? 1ull << 63 : 0ull;
+        a.min ^= flip;
+        a.max ^= flip;
+    } else {
+        const uint64_t ones = col.width >= 8u ? ~0ull : (1ull << (8u * col.width)) - 1ull;
+        a.sum = 0;
+        a.min = col.is_signed ? ones >> 1 : ones;
+        a.max = col.is_signed ? ~(ones >> 1) : 0ull;
+    }
+    return a;
+}
+
+// LDS tier: workgroup e folds entry e of the nparts scratch tables (n entries each) into groups[e]
+__global__ __launch_bounds__(256) void table_scan_group_fold_kernel(const AggAcc *__restrict__ part, uint32_t nparts,
+                                                                    uint32_t n, ScanAggCol col,
+                                                                    AggAcc *__restrict__ groups) {
+    __shared__ AggAcc s_part[4];
+    const uint32_t e = blockIdx.x;
+    AggAcc acc{0, 0, ~0ull, 0};
+    for (uint32_t b = threadIdx.x; b < nparts; b += blockDim.x) agg_add(acc, part[(uint64_t)b * n + e]);
+    agg_block_reduce(acc, s_part);
+    if (threadIdx.x == 0) groups[e] = group_record(acc, col);
+}
+
+// global tier, n entries of groups[]: fill -- the order-domain identities the scan launch starts
+// from; finish -- its entries in the column's domain (fresh: the record of an entry without a
+// record for every entry, nothing is read -- the empty leaf range of either tier)
+__global__ __launch_bounds__(256) void table_scan_group_fill_kernel(AggAcc *__restrict__ groups, uint64_t n) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x)
+        groups[k] = AggAcc{0, 0, ~0ull, 0};
+}
+__global__ __launch_bounds__(256) void table_scan_group_finish_kernel(AggAcc *__restrict__ groups, uint64_t n,
+                                                                      ScanAggCol col, bool fresh) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x)
+        groups[k] = group_record(fresh ? AggAcc{0, 0, ~0ull, 0} : groups[k], col);
+}
+
+// the LDS tier's grid: the aggregate's (a wave per leaf up to the grid cap -- a grid of a few
+// workgroups per CU measured slower here as it did there), bounded so that the scratch tables
+// stay within kGroupScratchMax: 16384 workgroups up to 127 groups, 8160 at 256
+constexpr uint64_t kGroupScratchMax = 64ull << 20;
+static bool group_lds_tier(uint32_t n_groups, const ScanGroupTuning &gt) {
+    return n_groups <= (gt.lds_max < 0 || (uint32_t)gt.lds_max > kGroupLdsMax ? kGroupLdsMax : (uint32_t)gt.lds_max);
+}
+static int group_lds_blocks(uint32_t nl, uint32_t n_groups, const ScanTuning &tune) {
+    const uint64_t bound = kGroupScratchMax / (((uint64_t)n_groups + 1) * sizeof(AggAcc));
+    const int mb = max_blocks(tune);
+    return grid_for(nl, 4, bound < (uint64_t)mb ? (int)bound : mb);
+}
+
+uint64_t table_scan_group_scratch_bytes(uint64_t nl, uint32_t n_groups, const ScanTuning &tune, const ScanGroupTuning &gt) {
+    if (!nl || !group_lds_tier(n_groups, gt)) return 0;
+    return (uint64_t)group_lds_blocks((uint32_t)nl, n_groups, tune) * ((uint64_t)n_groups + 1) * sizeof(AggAcc);
+}
+
+hipError_t launch_table_scan_group(const DevTable &t, uint32_t leaf0, uint32_t nl, bool snapshot, uint32_t rid,
+                                   const ScanPreds &preds, const ScanGroupSpec &grp, uint32_t agg_src, uint32_t agg_width,
+                                   bool agg_signed, uint64_t *groups, uint8_t *scratch, hipStream_t s,
+                                   const ScanTuning &tune, const ScanGroupTuning &gt) {
+    if ((uint64_t)leaf0 + nl > t.nleaves || !groups || !preds_fit(t, preds)) return hipErrorInvalidValue;
+    if (!column_fits(grp.width, grp.src, t.hstride) || grp.n == 0 || grp.n > kGroupMax) return hipErrorInvalidValue;
+    if (agg_width && !column_fits(agg_width, agg_src, t.hstride)) return hipErrorInvalidValue;
+    const ScanAggCol col{agg_src, agg_width, agg_signed ? 1u : 0u};
+    AggAcc *out = reinterpret_cast<AggAcc *>(groups);
+    const uint32_t n = grp.n + 1;
+    const int fill_blocks = grid_for(((uint64_t)n + 255) / 256, 1, 2048);
+    if (nl == 0) {
+        table_scan_group_finish_kernel<<<fill_blocks, 256, 0, s>>>(out, n, col, true);
+        return hipGetLastError();
+    }
+    const bool lds = group_lds_tier(grp.n, gt);
+    if (lds && !scratch) return hipErrorInvalidValue;
+    // combined by default: nothing in the LDS tier (64 lanes on one LDS entry measured no slower
+    // than the shuffles that would spare them), the first lane's group in the global tier
+    const uint32_t kmax = gt.combine >= 0 ? (uint32_t)gt.combine : lds ? 0u : 1u;
+    const ScanGroupCol gc{grp.src, grp.width, grp.is_signed ? 1u : 0u, grp.n,
+                          grp.is_signed ? grp.base ^ (1ull << 63) : grp.base, kmax};
+    const ScanPreds p = order_domain(preds);
+    if (lds) {
+        const int blocks = group_lds_blocks(nl, grp.n, tune);
+        const size_t shm = (size_t)n * sizeof(AggAcc);
+        AggAcc *part = reinterpret_cast<AggAcc *>(scratch);
+        if (snapshot) table_scan_group_kernel<true, true><<<blocks, 256, shm, s>>>(t, leaf0, nl, rid, p, gc, col, part);
+        else table_scan_group_kernel<false, true><<<blocks, 256, shm, s>>>(t, leaf0, nl, rid, p, gc, col, part);
+        table_scan_group_fold_kernel<<<n, 256, 0, s>>>(part, (uint32_t)blocks, n, col, out);
+    } else {
+        const int blocks = grid_for(nl, 4, max_blocks(tune));
+        table_scan_group_fill_kernel<<<fill_blocks, 256, 0, s>>>(out, n);
+        if (snapshot) table_scan_group_kernel<true, false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, gc, col, out);
+        else table_scan_group_kernel<false, false><<<blocks, 256, 0, s>>>(t, leaf0, nl, rid, p, gc, col, out);
+        table_scan_group_finish_kernel<<<fill_blocks, 256, 0, s>>>(out, n, col, false);
+    }
     return hipGetLastError();
 }
 

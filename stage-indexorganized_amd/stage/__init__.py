@@ -9,7 +9,7 @@ from .table import (PROBE_OUT_DTYPE, PROBE_OUT16_DTYPE, Q2_REC_DTYPE, ch_query2,
                     Reader, Stream, Table, device_count, pinned_empty, fastrandom, murmur64a_device, owner_rows, probe_sharded_loopback,
                     comm_allgather, comm_allreduce, rccl_info, set_shard_dedupe, set_shard_key_bits, sharded_stats,
                     sharded_stats_ex, window_stride, LEAF_END, TableScanResult, TableScanWhereResult, Pred,
-                    ycsb_ops, zipf_draws, zipf_zeta)
+                    Group, GroupAggregates, GROUP_MAX, GROUP_LDS_MAX, ycsb_ops, zipf_draws, zipf_zeta)
 
 __all__ = [
     "LIB_PATH", "SIGNATURES", "Q2_REC_DTYPE", "ch_query2", "ch_query2_batch", "ch_query2_batch_async", "StageError", "lib", "PROBE_OUT_DTYPE", "PROBE_OUT16_DTYPE", "Table", "DeviceBuffer", "Stream", "Event", "pinned_empty",
@@ -17,4 +17,5 @@ __all__ = [
     "rccl_info", "sharded_stats", "sharded_stats_ex", "comm_allreduce", "comm_allgather", "REPLY_ROWS", "REPLY_OWNER", "REPLY_PEER", "REPLY_DIRECT", "fastrandom", "ycsb_ops", "device_count", "ST_NOT_FOUND", "ST_LATEST", "ST_COPY", "ST_OLD",
     "ST_FAIL_INVALID_TS", "ST_CHAIN_MISS", "RC_OK", "RC_INVALID", "RC_KEY_EXISTS", "RC_NOT_FOUND",
     "RC_NOT_NEEDED_UPDATE", "RC_DIRTY", "window_stride", "LEAF_END", "TableScanResult", "TableScanWhereResult", "Pred",
+    "Group", "GroupAggregates", "GROUP_MAX", "GROUP_LDS_MAX",
 ]

@@ -45,7 +45,23 @@ class ScanAgg(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("sum", ctypes.c_int64), ("min", ctypes.c_int64), ("max", ctypes.c_int64)]
 
 
+class ScanGroup(ctypes.Structure):
+    """stage_scan_group"""
+    _fields_ = [
+        ("off", ctypes.c_uint32),
+        ("width", ctypes.c_uint8),
+        ("is_signed", ctypes.c_uint8),
+        ("in_key", ctypes.c_uint8),
+        ("pad", ctypes.c_uint8),
+        ("base", ctypes.c_int64),
+        ("n_groups", ctypes.c_uint32),
+        ("pad2", ctypes.c_uint32),
+    ]
+
+
 PRED_MAX = 4  # STAGE_PRED_MAX
+GROUP_MAX = 1 << 24  # STAGE_GROUP_MAX
+GROUP_LDS_MAX = 256  # STAGE_GROUP_LDS_MAX
 
 # every exported symbol: name -> (restype, argtypes)
 SIGNATURES = {
@@ -162,6 +178,10 @@ SIGNATURES = {
                                                      c_vp]),
     "stage_table_scan_aggregate": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_uint32,
                                                   ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
+    "stage_table_scan_group_aggregate": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
+                                                        ctypes.c_uint32, c_vp, ctypes.c_uint32, ctypes.c_uint32,
+                                                        ctypes.c_uint32, c_vp, c_vp]),
+    "stage_set_scan_group_tuning": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
     "stage_resolve_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, c_vp, c_vp]),
     "stage_set_probe_tuning": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
     "stage_set_scan_tuning": (ctypes.c_int, [c_vp, ctypes.c_int]),

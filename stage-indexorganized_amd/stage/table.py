@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import ScanAgg, ScanPred, StageParams, c_vp, check, lib
+from ._lib import GROUP_LDS_MAX, GROUP_MAX, ScanAgg, ScanGroup, ScanPred, StageParams, c_vp, check, lib  # noqa: F401
 
 PROBE_OUT_DTYPE = np.dtype([
     ("status", "u1"), ("flags", "u1"), ("hops", "u2"), ("leaf", "u4"), ("slot", "u2"), ("key_len", "u2"),
@@ -74,6 +74,30 @@ def _pack_preds(preds):
             a.payload_off, a.width, a.is_signed, a.negate = p.off, p.width, int(p.signed), int(p.negate)
             a.lo, a.hi = _i64(p.lo), _i64(p.hi)
     return arr, len(preds)
+
+
+class Group(collections.namedtuple("Group", "off width base n_groups signed in_key")):
+    """The group column of a grouped aggregate (stage_scan_group): the little-endian integer
+    column of `width` (1, 2, 4, 8) bytes at payload offset `off` -- with in_key at byte `off` of
+    the row's key field -- sign- or zero-extended; a record whose value is base + g belongs to
+    group g < n_groups (Python-integer arithmetic, nothing wraps), every other record to the
+    rest group n_groups.  base is a Python int in the column's domain."""
+    __slots__ = ()
+
+    def __new__(cls, off, width, base, n_groups, signed=False, in_key=False):
+        return super().__new__(cls, int(off), int(width), int(base), int(n_groups), bool(signed), bool(in_key))
+
+
+# Table.table_scan_group_aggregate: numpy arrays of n_groups + 1 entries, the last the rest group
+GroupAggregates = collections.namedtuple("GroupAggregates", "count sum min max")
+
+
+def _pack_group(group):
+    """-> a stage_scan_group (or None); it must outlive the call"""
+    if group is None or isinstance(group, ScanGroup):
+        return group
+    g = group if isinstance(group, Group) else Group(*group)
+    return ScanGroup(g.off, g.width, int(g.signed), int(g.in_key), 0, _i64(g.base), g.n_groups, 0)
 
 
 def _ptr(a):
@@ -886,6 +910,37 @@ class Table:
         w = d_agg.to_numpy(np.uint64, 4)
         signed = agg is not None and bool(agg[2])
         return (int(w[0]),) + tuple(_i64(int(x)) if signed else int(x) for x in w[1:])
+
+    def table_scan_group_aggregate_device(self, leaves, read_id, preds, group, agg, d_groups, stream=None):
+        """stage_table_scan_group_aggregate into d_groups (32 * (n_groups + 1) bytes of device
+        memory: count, sum, min, max per group, the rest group last); group = a Group, agg =
+        (payload_off, width, signed) or None for the counts alone.  Enqueued on `stream`."""
+        begin, end, rid = _scan_range(leaves, read_id)
+        p = _dev
+        arr, n = _pack_preds(preds)
+        g = _pack_group(group)
+        off, width, signed = (0, 0, False) if agg is None else agg
+        check(lib().stage_table_scan_group_aggregate(self.h, begin, end, rid, arr, n, ctypes.byref(g) if g else None,
+                                                     off, width, int(signed), p(d_groups), p(stream)),
+              "stage_table_scan_group_aggregate")
+
+    def table_scan_group_aggregate(self, leaves=None, read_id=None, preds=(), group=None, agg=None):
+        """table_scan_aggregate per group: GroupAggregates(count, sum, min, max), numpy arrays of
+        group.n_groups + 1 entries -- entry g over the records table_scan_where selects whose
+        group column holds group.base + g, the last entry over every other selected record.
+        count is uint64; sum (modulo 2**64), min and max are int64 for a signed aggregate column,
+        else uint64; an entry without a record: count 0, sum 0, min = the domain's largest value,
+        max = its smallest.  agg None: the counts, and zeros."""
+        g = _pack_group(group)
+        if g is None:
+            raise ValueError("table_scan_group_aggregate needs a group")
+        n = int(g.n_groups) + 1 if 1 <= g.n_groups <= GROUP_MAX else 1  # a bad n_groups is the library's error
+        d_groups = DeviceBuffer(32 * n)
+        self.table_scan_group_aggregate_device(leaves, read_id, preds, g, agg, d_groups)
+        check(lib().stage_device_sync(), "sync")
+        w = d_groups.to_numpy(np.uint64, 4 * n).reshape(n, 4)
+        t = np.int64 if agg is not None and bool(agg[2]) else np.uint64
+        return GroupAggregates(w[:, 0].copy(), w[:, 1].astype(t), w[:, 2].astype(t), w[:, 3].astype(t))
 
     def index_scan_first(self, start_keys, scan_size, prefix_words, read_ids=None):
         """index_scan consumed up to its first LATEST / OLD tuple carrying the start key's first
