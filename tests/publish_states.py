@@ -24,9 +24,17 @@ Inserts of P1, P2 and P4 go only into leaves with room to spare, so no leaf spli
 leaves before and at the emptied leaf stay out of every random pick, and the emptied leaf and the
 leaf with the empty group take no inserts, so those states last to the end.
 
+Device epochs (test_gpu_device_epochs.py; on the CPU the same epochs go through the host's per-key
+calls): draw_epoch() draws the ops of one stage_update_batch_device call from every state the
+script has made -- live, hot, in-flight, deleted, aborted, held-back and absent keys -- and
+device_epoch() applies them to the device and, op by op, to the oracle.  EPOCH_STEPS puts such
+epochs between the publishes of the phases; finish_device_flying() lets the host commit and abort
+updates the device left in flight.
+
 expected_reads() draws the inputs of every read entry point and computes what the oracle answers
 (no device); compare_reads() holds the device against that, exactly; check_all_reads() is both.
 """
+import collections
 import functools
 import zlib
 
@@ -34,6 +42,7 @@ import numpy as np
 
 import oracle_lib as O
 import stage
+from stage._lib import check
 from table_scan_expect import LAST, M_VISIBLE, raw_expect, snapshot_expects
 from test_gpu_probe_window import check_status, check_window
 from test_gpu_scan_window import check_scan
@@ -60,6 +69,20 @@ def tpcc_keys(width, n, seed):
 
 SMALL_LEAVES = dict(leaf_node_size=4096, split_threshold=3072, merge_threshold=1024)    # varlen_family's
 LARGE_LEAVES = dict(leaf_node_size=32768, split_threshold=8192, merge_threshold=16384)  # key8_large_leaves'
+
+Epoch = collections.namedtuple("Epoch", "keys deltas wid cid sst window hot hot2 where head_repeat")
+# the GPU test's steps (test_gpu_device_epochs.py): the write phases and, between their publishes,
+# device epochs -- per epoch (window, sst_mode, head_repeat, old_hot) of State.draw_epoch
+EPOCH_STEPS = ("P0", "P1", "E1", "P2", "E2", "E3", "P3", "P4", "E4", "E5")
+FINISH_BEFORE = ("P2", "P3")  # phases before which the host finishes updates the epochs left in flight
+EPOCH_SEED = 11               # of the generator the epochs are drawn from, on the CPU and on the device
+EPOCHS = {
+    "E1": [("whole", None, False, False)],
+    "E2": [("last", "mixed", True, True)],
+    "E3": [("odd", "mixed", False, False), ("odd", None, True, True)],  # back to back on one stream
+    "E4": [("bad", "mixed", False, False)],                             # no op may succeed
+    "E5": [("whole", "mixed", False, False)],                           # every chunk of the row a second time
+}
 
 GEOMETRIES = {
     # name: (key width, payload, table parameters, key set in load order, leaf capacities, key words)
@@ -116,6 +139,9 @@ class State:
         self.deleted, self.inflight, self.aborted, self.abort_counts = [], [], [], []
         self.phase = None
         self.seen, self.stops = set(), 0  # statuses the device returned; scans that ended at the emptied leaf
+        self.dev_flying = []    # keys whose update an epoch left in flight, until a host phase finishes them
+        self.sst_probes = []    # (key, read id) pairs around the end stamps of an epoch's retired versions
+        self.rc_seen = set()    # return codes of the epochs
 
     # -------------------------------------------------------------------------------- both sides
     def same(self, what, key, a, b):
@@ -163,31 +189,46 @@ class State:
         self.aborted.append(k)
         self.abort_counts.append((before, self.counts(leaf)))
 
+    def flies(self, k, rc):
+        if rc == stage.RC_OK:
+            self.busy.add(k)
+        return rc
+
+    def lands(self, k, rc):
+        if rc == stage.RC_OK:
+            self.busy.discard(k)
+        return rc
+
     def update(self, k, wid):
         off, d = self.delta()
-        return self.same("update", k, self.tab.update_key(k, off, d, wid), self.orc.update(k, len(k), off, d, wid))
+        return self.flies(k, self.same("update", k, self.tab.update_key(k, off, d, wid),
+                                       self.orc.update(k, len(k), off, d, wid)))
 
     def update_owned(self, k, wid):
         off, d = self.delta()
         return self.same("update_owned", k, self.tab.update_key_owned(k, off, d, wid),
                          self.orc.update_owned(k, len(k), off, d, wid))
 
-    def commit_update(self, k, cid):
-        return self.same("commit_update", k, self.tab.commit_update_key(k, cid, cid),
-                         self.orc.commit_update(k, len(k), cid, cid))
+    def commit_update(self, k, cid, sst=None):
+        sst = cid if sst is None else sst
+        return self.lands(k, self.same("commit_update", k, self.tab.commit_update_key(k, cid, sst),
+                                       self.orc.commit_update(k, len(k), cid, sst)))
 
     def abort_update(self, k):
-        return self.same("abort_update", k, self.tab.abort_update_key(k), self.orc.abort_update(k, len(k)))
+        return self.lands(k, self.same("abort_update", k, self.tab.abort_update_key(k),
+                                       self.orc.abort_update(k, len(k))))
 
     def finalize_update(self, k, cid):
         """the library's finalize_update takes keys of up to 8 bytes only"""
-        return self.same("finalize_update", k, self.tab.finalize_update(int.from_bytes(k, "little"), cid, len(k)),
-                         self.orc.finalize_update(k, len(k), cid))
+        return self.lands(k, self.same("finalize_update", k,
+                                       self.tab.finalize_update(int.from_bytes(k, "little"), cid, len(k)),
+                                       self.orc.finalize_update(k, len(k), cid)))
 
     def gone(self, k, rc):
         if rc in (stage.RC_OK, stage.RC_INVALID):  # RC_INVALID: under the merge threshold, deleted all the same
             self.live.pop(k, None)
             self.deleted.append(k)
+            self.busy.discard(k)
         return rc
 
     def delete(self, k, cid):
@@ -354,7 +395,6 @@ class State:
         cid = self.stamp()
         for k in self.flying:
             self.commit_update(k, cid)
-        self.busy = set()
         wid, cid = self.stamp(), self.stamp()
         for k in self.twice[:40]:
             self.update(k, wid)
@@ -394,6 +434,8 @@ class State:
         for k in [k for k in self.inflight if k not in flying]:
             self.inflight.remove(k)
             self.live[k] = None
+        self.busy &= flying  # ... and so is an update in flight there (its copy stays behind the record)
+        self.dev_flying = [k for k in self.dev_flying if k in self.busy]
         self.halves = None
         for ks in fed:  # a fed leaf whose keys now route to two leaves has split
             ids = self.leaf_of(ks)
@@ -419,6 +461,214 @@ class State:
         for leaf in self.roomy[:4]:
             for k in self.take(leaf, 1):
                 self.insert(k, cid2)
+
+    # -------------------------------------------------------------------------------- device epochs
+    def window(self, kind):
+        """the (payload offset, length) every op of an epoch patches"""
+        p = self.payload
+        return {"whole": (0, p), "last": (p - 1, 1), "odd": (5, 151) if p >= 156 else (1, p - 3),
+                "bad": (p - 1, 4)}[kind]  # bad: past the payload's end
+
+    def column(self, k, window):
+        """the record's current bytes of the window, as the leaf holds them (in flight or not)"""
+        _, rec = self.orc.read(k, len(k), for_update=True)
+        return rec[self.key_pad + window[0]:self.key_pad + sum(window)].tobytes()
+
+    def neighbours(self, rng, calm):
+        """two keys of `calm` in neighbouring slots of one leaf"""
+        v = self.view()
+        for a in rng.permutation(len(v)).tolist():
+            l = v[a]
+            for i in range(l.count - 1):
+                if l.vis[i] and l.vis[i + 1] and l.keys[i] in calm and l.keys[i + 1] in calm:
+                    return [l.keys[i], l.keys[i + 1]]
+        raise AssertionError((self.name, "no two calm keys in neighbouring slots"))
+
+    def draw_epoch(self, rng, m, window, sst_mode, head_repeat=False, old_hot=False, avoid=()):
+        """One epoch of m ops that all patch `window` -> Epoch(keys, deltas, wid, cid, sst, ...);
+        nothing touches the device.  The ops, in random batch order:
+          * a hot key 200 times, deltas of a 3-letter alphabet (OK and NOT_NEEDED_UPDATE interleave:
+            at least kJumpFrom = 128 ops follow its first failure, the pointer-jump finisher's
+            groups; with old_hot some of its writers are older than the record and the group is
+            walked instead); head_repeat: its first op repeats the record's current column;
+          * a second hot key 70 times (the wave finisher, across a 64-op chunk), op 35 succeeds and
+            is left uncommitted: the rest of the group is DIRTY;
+          * two keys in neighbouring slots of one leaf 40 times each (two groups in one chunk);
+          * every in-flight insert and 40 keys with a host update in flight (DIRTY);
+          * deleted, aborted, held-back and absent keys (NOT_FOUND), and for variable-length keys
+            ten live keys with a trailing zero byte: the same key word, another length (NOT_FOUND);
+          * live keys at random for the rest (about two thirds of m): a tenth left uncommitted, a
+            twentieth with the record's current column as their delta (NOT_NEEDED_UPDATE);
+          * about 3 % of all ops with writer id 1 (NOT_NEEDED_UPDATE by cstamp).
+        Ids: wid = b + 4 i, cid = wid + 2 (0: uncommitted); sst_mode None passes no end stamps,
+        "mixed" one of cid - 2, cid - 1, cid, cid + 1 per op (never 0).  cid - 2 is the only one
+        of them with a read id strictly between end stamp and commit id (ids are integers): reads
+        at cid - 1 miss the chain there, and sst_probes collects those.  Every id goes to
+        self.cids.  avoid: keys the hot picks leave out (those of an epoch drawn before this one and
+        not yet applied, which may change their column or leave them in flight)."""
+        off, ln = window
+        bad = off + ln > self.payload
+        pool = [k for k in self.live if k not in self.quiet]
+        calm = {k for k in pool if k not in self.busy and k not in avoid}
+        pair = self.neighbours(rng, calm)
+        rest = sorted(calm - set(pair))
+        hot, hot2 = (rest[i] for i in rng.choice(len(rest), 2, replace=False))
+        letters = [bytes([c]) * ln for c in rng.choice(256, 3, replace=False).tolist()]
+        ops = []  # [key, delta, committed, may take writer id 1, (group, index in it) of the hot groups' ops]
+        seq = rng.integers(0, 3, 200).tolist()
+        ops += [[hot, letters[c], True, old_hot, ("hot", j)] for j, c in enumerate(seq)]
+        if head_repeat and not bad:
+            ops[0][1] = self.column(hot, window)
+        seq = rng.integers(0, 3, 70).tolist()
+        seq[35] = (seq[34] + 1) % 3  # differs from the column the ops before it left: succeeds
+        ops += [[hot2, letters[c], j != 35, False, ("hot2", j)] for j, c in enumerate(seq)]
+        for k in pair:
+            ops += [[k, letters[c], True, True, None] for c in rng.integers(0, 3, 40).tolist()]
+        others = (self.inflight + self.some(rng, sorted(self.busy), 40) + self.some(rng, self.deleted, 60)
+                  + self.aborted + self.some(rng, self.held, 60) + [self.absent_key(rng) for _ in range(60)])
+        if self.width == 0:
+            others += [k + b"\0" for k in self.some(rng, [k for k in pool if len(k) < 8], 10)]
+        ops += [[k, self.bytes_rng(rng, ln), True, True, None] for k in others]
+        pool = [k for k in pool if k not in (hot, hot2, *pair)]
+        for k in (pool[i] for i in rng.integers(0, len(pool), max(m - len(ops), 0))):
+            u = rng.random()
+            d = self.column(k, window) if u < 0.05 and not bad else self.bytes_rng(rng, ln)
+            ops.append([k, d, not 0.05 <= u < 0.15, True, None])
+        ops = [ops[i] for i in self.keep_order(rng, ops)]
+        n = len(ops)
+        b = (self.cid + 8) // 4 * 4
+        self.cid = b + 4 * n + 4
+        wid = (b + 4 * np.arange(n)).astype(np.uint32)
+        cid = wid + np.uint32(2)
+        old = (rng.random(n) < 0.03) & np.array([o[3] for o in ops])
+        sst = None
+        used = set(wid.tolist()) | set(cid.tolist())
+        if sst_mode == "mixed":
+            sst = (cid.astype(np.int64) + rng.integers(-2, 2, n)).astype(np.uint32)
+            used |= set(sst.tolist())
+        else:
+            assert sst_mode is None, sst_mode
+        self.cids += sorted(used)
+        wid[old] = 1
+        cid[~np.array([o[2] for o in ops])] = 0
+        deltas = np.frombuffer(b"".join(o[1] for o in ops), np.uint8).reshape(n, ln)
+        where = {o[4]: i for i, o in enumerate(ops) if o[4]}
+        return Epoch([o[0] for o in ops], deltas, wid, cid, sst, window, hot, hot2, where, head_repeat and not bad)
+
+    def bytes_rng(self, rng, n):
+        return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+
+    def keep_order(self, rng, ops):
+        """a random batch order that keeps each key's ops in the order drawn"""
+        pos = rng.permutation(len(ops)).tolist()  # the batch positions dealt out, one per op
+        by_key = collections.defaultdict(list)
+        for i, o in enumerate(ops):
+            by_key[o[0]].append(i)
+        out = [None] * len(ops)
+        for drawn in by_key.values():  # the key's positions, lowest first, take its ops as drawn
+            for at, i in zip(sorted(pos[j] for j in drawn), drawn):
+                out[at] = i
+        return out
+
+    def epoch_on_oracle(self, ep):
+        """the epoch applied to the oracle op by op -> its return codes"""
+        off = ep.window[0]
+        rc = np.zeros(len(ep.keys), np.uint8)
+        for i, k in enumerate(ep.keys):
+            r = self.orc.update(k, len(k), off, ep.deltas[i].tobytes(), int(ep.wid[i]))
+            if r == stage.RC_OK and ep.cid[i]:
+                r = self.orc.commit_update(k, len(k), int(ep.cid[i]), int(ep.cid[i] if ep.sst is None else ep.sst[i]))
+            rc[i] = r
+        return rc
+
+    def note_epoch(self, ep, codes):
+        """the State's books after an epoch with these codes"""
+        self.rc_seen |= set(codes.tolist())
+        for i in np.nonzero((codes == stage.RC_OK) & (ep.cid == 0))[0]:
+            self.busy.add(ep.keys[i])
+            self.dev_flying.append(ep.keys[i])
+        if ep.sst is not None:  # retired versions that end two ids before the commit
+            gap = np.nonzero((codes == stage.RC_OK) & (ep.cid != 0) & (ep.sst + np.uint32(2) == ep.cid))[0]
+            at = gap[np.linspace(0, gap.size - 1, min(gap.size, 40)).astype(int)] if gap.size else gap
+            self.sst_probes += [(ep.keys[i], int(ep.cid[i]) - d) for i in at for d in (1, 2)]
+        return codes
+
+    def same_codes(self, what, ep, rc, exp):
+        bad = np.nonzero(rc != exp)[0]
+        assert bad.size == 0, (self.name, what, bad.size, [(int(i), ep.keys[i], int(rc[i]), int(exp[i]),
+                                                            int(ep.wid[i]), int(ep.cid[i])) for i in bad[:8]])
+
+    def device_args(self, ep):
+        """the epoch's arguments of update_batch_device, after the keys: their lens last"""
+        words, lens = self.pack(ep.keys)
+        return words, (ep.window[0], ep.deltas, ep.wid, ep.cid, ep.sst, lens)
+
+    def device_epoch(self, ep):
+        """the epoch applied by the device and, op by op, by the oracle: equal codes"""
+        words, rest = self.device_args(ep)
+        rc, n_ok = self.tab.update_batch_device(words, *rest)
+        exp = self.epoch_on_oracle(ep)
+        self.same_codes("device epoch", ep, rc, exp)
+        assert n_ok == int((exp == stage.RC_OK).sum()), (self.name, n_ok)
+        return self.note_epoch(ep, exp)
+
+    def device_epochs_pipelined(self, eps):
+        """the epochs enqueued back to back on one stream, no host wait between them"""
+        s = stage.Stream()
+        calls = []
+        for ep in eps:
+            words, (off, deltas, wid, cid, sst, lens) = self.device_args(ep)
+            words = self.tab.key_buffer(words)[0]
+            d = [None if a is None else stage.DeviceBuffer.from_numpy(np.ascontiguousarray(a))
+                 for a in (words, lens, deltas.reshape(-1), wid, cid, sst)]
+            ptr = [None if x is None else x.ptr for x in d]
+            rcb = stage.DeviceBuffer(len(ep.keys))
+            check(stage.lib().stage_update_batch_device(self.tab.h, ptr[0], ptr[1], len(ep.keys), off, ptr[2],
+                                                        deltas.shape[1], ptr[3], ptr[4], ptr[5], rcb.ptr, None, s.ptr),
+                  "update_batch_device")
+            calls.append((ep, rcb, d))
+        s.sync()
+        out = []
+        for ep, rcb, _ in calls:
+            exp = self.epoch_on_oracle(ep)
+            self.same_codes("pipelined epoch", ep, rcb.to_numpy(np.uint8, len(ep.keys)), exp)
+            out.append(self.note_epoch(ep, exp))
+        return out
+
+    def apply_epoch_on_host(self, ep):
+        """the same epoch through the host's per-key calls, and the oracle's -> the codes"""
+        off = ep.window[0]
+        rc = np.zeros(len(ep.keys), np.uint8)
+        for i, k in enumerate(ep.keys):
+            d, w, c = ep.deltas[i].tobytes(), int(ep.wid[i]), int(ep.cid[i])
+            r = self.same("epoch update", k, self.tab.update_key(k, off, d, w), self.orc.update(k, len(k), off, d, w))
+            if r == stage.RC_OK and c:
+                sst = c if ep.sst is None else int(ep.sst[i])
+                r = self.same("epoch commit", k, self.tab.commit_update_key(k, c, sst),
+                              self.orc.commit_update(k, len(k), c, sst))
+            rc[i] = r
+        return self.note_epoch(ep, rc)
+
+    def finish_device_flying(self, rng):
+        """the host finishes updates whose copy headers the device wrote: half of those the epochs
+        left in flight are committed, a quarter aborted, the rest stay in flight"""
+        ks = [k for k in dict.fromkeys(self.dev_flying) if k in self.busy]
+        ks = [ks[i] for i in rng.permutation(len(ks))]
+        cid = self.stamp()
+        for k in ks[:len(ks) // 2]:
+            assert self.commit_update(k, cid) == stage.RC_OK, k
+        for k in ks[len(ks) // 2:3 * len(ks) // 4]:
+            assert self.abort_update(k) == stage.RC_OK, k
+        self.dev_flying = []
+        return len(ks)
+
+    def draw_step(self, rng, step, m=2000):
+        """the epochs of one step of EPOCH_STEPS, drawn before any of them is applied"""
+        eps = []
+        for kind, sst_mode, head_repeat, old_hot in EPOCHS[step]:
+            avoid = {k for ep in eps for k in ep.keys}
+            eps.append(self.draw_epoch(rng, m, self.window(kind), sst_mode, head_repeat, old_hot, avoid))
+        return eps
 
     # -------------------------------------------------------------------------------- the oracle's answers
     def read_id_pool(self):
@@ -464,6 +714,8 @@ class State:
         x.keys = (self.some(rng, self.everything, 200) + self.some(rng, self.deleted, 40) + self.inflight
                   + self.aborted + self.some(rng, sorted(self.busy), 20) + [self.absent_key(rng) for _ in range(20)])
         x.rids = rng.choice(pool, len(x.keys)).astype(np.uint32)
+        x.keys += [k for k, _ in self.sst_probes]  # just below and inside the gap end stamp .. commit id
+        x.rids = np.concatenate([x.rids, np.array([r for _, r in self.sst_probes], np.uint32)])
         x.reads = {True: self.oracle_reads(x.keys, x.rids), False: self.oracle_reads(x.keys, None)}
         n = self.payload // 2
         x.window = (n, min(7, self.payload - n))

@@ -197,7 +197,7 @@ def test_device_epoch_edge_cases(gpu):
                                                                        (62, False, True, False), (3, False, False, True),
                                                                        (62, False, True, True)])
 def test_hot_key_groups_finished_by_workgroups(gpu, alphabet, old_writers, head_fails, adjacent):
-    """Groups longer than the workgroup finisher's threshold (2048 ops from the first failure):
+    """Groups longer than the workgroup finisher's threshold (kJumpFrom = 128 ops from the first failure on):
     three hot keys hammered ~6000 times each in one epoch with a 3-letter delta alphabet
     (NotNeededUpdate and successes interleave) or RunMixed's 256 / 62 (successes with sparse
     failures), a few left in flight (the rest of that group DIRTY) -- return codes, versions and

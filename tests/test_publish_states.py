@@ -7,6 +7,10 @@ an empty slot group beside live ones, a leaf with records but none visible, visi
 leaf's sorted ones, an in-flight insert without a copy, a record count that fell with an aborted
 insert and rose again, and scans that end at the emptied leaf.  The oracle's answers for every
 read entry point are computed too, so the GPU test's inputs are known to be valid before it runs.
+
+test_epoch_script_reaches_its_codes does the same for the steps of test_gpu_device_epochs.py, with
+every epoch applied through the host's per-key calls instead of the device: host and oracle stay
+identical, and the oracle's codes show that every epoch holds the cases it was drawn for.
 """
 import ctypes
 
@@ -15,7 +19,7 @@ import pytest
 
 import oracle_lib as O
 import stage
-from publish_states import GEOMETRIES, M_CONTROL, PHASES, State
+from publish_states import EPOCH_SEED, EPOCH_STEPS, FINISH_BEFORE, GEOMETRIES, M_CONTROL, PHASES, State
 from scan_semantics import LeafScanner
 from test_host_layout import compare_layout
 
@@ -93,4 +97,76 @@ def test_script_reaches_its_states(name):
                     exp = np.ascontiguousarray(orows[i, :oc[i], :8]).view(np.uint64).reshape(-1)
                     assert np.array_equal(got, exp), (phase, i, size)
     assert leaves["P0"] == leaves["P1"] == leaves["P2"] < leaves["P3"] == leaves["P4"]
+    assert st.halves and all(len(h) > 30 for h in st.halves)
+
+
+def same_tables(st):
+    compare_layout(st.tab, st.orc)
+    b, sk, sl = st.tab.export_leaf_images()
+    ob, osk, osl = st.orc.export_leaf_images(kwords=st.kw)
+    assert np.array_equal(b, ob) and np.array_equal(sk, osk) and np.array_equal(sl, osl)
+    assert st.tab.stats()["versions"] == st.orc.stats()["versions"]
+
+
+def check_epoch(st, step, ep, codes, new_probes):
+    """the oracle's codes alone: the epoch reaches what it was drawn for"""
+    n = {rc: int((codes == rc).sum()) for rc in (stage.RC_OK, stage.RC_NOT_FOUND, stage.RC_NOT_NEEDED_UPDATE,
+                                                 stage.RC_DIRTY, stage.RC_INVALID)}
+    what = (st.name, step, n)
+    group = codes[[i for i, k in enumerate(ep.keys) if k == ep.hot]]
+    assert group.size == 200, what
+    fails = np.nonzero(group != stage.RC_OK)[0]
+    assert fails.size and 200 - fails[0] >= 128, what  # kJumpFrom ops from the first failure on
+    if step == "E4":  # past the payload: INVALID on a live record, DIRTY in flight, NOT_FOUND
+        assert n[stage.RC_OK] == 0 and min(n[stage.RC_INVALID], n[stage.RC_DIRTY], n[stage.RC_NOT_FOUND]) >= 20, what
+        assert sum(n.values()) == codes.size and not new_probes, what
+        return
+    assert n[stage.RC_OK] >= 0.3 * codes.size and n[stage.RC_INVALID] == 0, what
+    assert min(n[stage.RC_NOT_FOUND], n[stage.RC_NOT_NEEDED_UPDATE], n[stage.RC_DIRTY]) >= 20, what
+    # both codes interleave in the hot group; the second hot group is DIRTY behind its uncommitted op
+    assert (group == stage.RC_OK).sum() >= 40 and (group == stage.RC_NOT_NEEDED_UPDATE).sum() >= 40, what
+    at = ep.where[("hot2", 35)]
+    group2 = codes[[i for i, k in enumerate(ep.keys) if k == ep.hot2]]
+    assert codes[at] == stage.RC_OK and ep.cid[at] == 0 and (group2[36:] == stage.RC_DIRTY).all(), what
+    if ep.head_repeat:
+        assert codes[ep.where[("hot", 0)]] == stage.RC_NOT_NEEDED_UPDATE, what
+    for k in st.inflight:  # an insert in flight is found by the locate probe and must be DIRTY
+        assert all(codes[i] == stage.RC_DIRTY for i, x in enumerate(ep.keys) if x == k), what
+    if st.width == 0:  # a live key's bytes and one more zero byte: the same key word, not the key
+        longer = [i for i, k in enumerate(ep.keys) if k.endswith(b"\0")]
+        assert len(longer) == 10 and (codes[longer] == stage.RC_NOT_FOUND).all(), what
+    if ep.sst is None:
+        assert not new_probes, what
+        return
+    # a retired version that ends two ids before the commit: a read between them finds no version
+    assert len(new_probes) >= 20, what
+    for k, rid in new_probes:
+        out, _ = st.orc.read(k, len(k), rid)
+        assert out["status"] == (stage.ST_CHAIN_MISS if rid % 4 == 1 else stage.ST_OLD), (what, k, rid, out)
+        assert st.orc.read(k, len(k), rid | 3)[0]["status"] in (stage.ST_LATEST, stage.ST_OLD, stage.ST_COPY), what
+
+
+@pytest.mark.parametrize("name", list(GEOMETRIES))
+def test_epoch_script_reaches_its_codes(name):
+    st = State(name)
+    rng, erng = np.random.default_rng(5), np.random.default_rng(EPOCH_SEED)
+    for step in EPOCH_STEPS:
+        if step in PHASES:
+            if step in FINISH_BEFORE:
+                assert st.finish_device_flying(erng) >= 8, (name, step)
+            st.run(step)
+        else:
+            eps = st.draw_step(erng, step)
+            for ep in eps:
+                before = len(st.sst_probes)
+                codes = st.apply_epoch_on_host(ep)
+                check_epoch(st, step, ep, codes, st.sst_probes[before:])
+        assert st.busy == {k for l in st.view() for k, m in zip(l.keys, l.meta.tolist())
+                           if m & M_CONTROL and k not in st.inflight}, (name, step)
+        same_tables(st)
+        x = st.expected_reads(rng)
+        if step in ("P2", "P3", "P4", "E5"):  # the states the phases made last through the epochs
+            check_states(st, "P2" if step == "P2" else "P4", x)
+    assert st.rc_seen >= {stage.RC_OK, stage.RC_NOT_FOUND, stage.RC_NOT_NEEDED_UPDATE, stage.RC_DIRTY,
+                          stage.RC_INVALID}
     assert st.halves and all(len(h) > 30 for h in st.halves)
