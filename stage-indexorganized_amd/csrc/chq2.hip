@@ -35,6 +35,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "handle.hpp"
+#include "tuple_read.hpp"
 #include "visibility.hpp"
 #include "wave.hpp"
 
@@ -46,12 +47,6 @@ namespace {
 constexpr int kRegionScan = 6, kNationScan = 65;  // scan_sz of :653 and :734
 constexpr uint32_t kIDataOff = 4 + 32 + 8;         // I_DATA in Item's payload (I_IM_ID, I_NAME, I_PRICE)
 static const char *const kRegions[] = {"AFRICA", "AMERICA", "ASIA", "EUROPE", "MIDDLE EAST"};
-
-__device__ __forceinline__ bool produced(uint32_t st) { return st == ST_LATEST || st == ST_COPY || st == ST_OLD; }
-
-__device__ __forceinline__ int32_t ld_i32(const uint8_t *p) {
-    return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-}
 
 // blocks copy the visited suppliers' map entries (2 words each) to their segments; counts[0] =
 // the number of visited suppliers (q2_sel_start); nothing is written past m_cap keys (the host
@@ -466,7 +461,7 @@ __global__ void q2_reduce(DevTable st, const stage_probe_out_dev *__restrict__ s
         const u32x4 *bp = reinterpret_cast<const u32x4 *>(sbase + klast);
         u32x4 a = bp[0], b = bp[1];
         revisit_one(st, rids[q], a, b);
-        if (produced(a.x & 0xFF)) {
+        if (produced_tuple(a.x & 0xFF)) {
             const uint8_t *row = st.heap + (uint64_t)b.z * st.hstride + skpad;
             r.s_quantity = ld_i32(row);
             r.s_ytd = ld_i32(row + 4);
@@ -507,7 +502,7 @@ __global__ __launch_bounds__(256) void q2_finish(DevTable it, const stage_probe_
         revisit_one(it, rids[s / n], ia, ib);
         const uint32_t st = ia.x & 0xFF;
         stage_q2_rec r = out[s];
-        if (!produced(st)) {
+        if (!produced_tuple(st)) {
             atomicOr(abort_flag + s / n, 1);
         } else {
             // I_DATA's 64 bytes in 16 word loads issued together (4-B aligned), scanned in registers
@@ -550,444 +545,550 @@ __global__ __launch_bounds__(256) void q2_finish(DevTable it, const stage_probe_
     }
 }
 
-// TableScanExecutor rows of one scan from `start` (device scan) into the table's scratch: the
-// returned pointer is the first row, the row count (u32) 8 bytes before it
-// (d_start: the start key, in device memory written before s reaches the scan)
-uint8_t *scan_rows_buf(stage_table *t, uint32_t scan_size) {
-    return scratch_bytes(t->dev, 64 + (uint64_t)scan_size * t->dev.view.stride) + 64;
-}
-// ... and both CH-Q2 dimension scans (REGION, NATION) from the same start key: one launch when
-// launch_scan_pair takes them, else one each
-void scan_dims(stage_table *a, uint32_t sa, stage_table *b, uint32_t sb, const uint64_t *d_start, hipStream_t s,
-               const uint8_t **ra, const uint8_t **rb) {
-    uint8_t *pa = scan_rows_buf(a, sa), *pb = scan_rows_buf(b, sb);
-    auto cnt = [](uint8_t *rows) { return (uint32_t *)(rows - 8); };  // 8 bytes before the rows
-    const DevTable &va = a->dev.view, &vb = b->dev.view;
-    if (scan_pair_supported(va, sa, vb, sb)) {
-        hip_check(launch_scan_pair(va, d_start, sa, cnt(pa), pa, vb, d_start, sb, cnt(pb), pb, s), "scan pair");
-    } else {
-        hip_check(launch_scan(va, d_start, nullptr, 1, sa, cnt(pa), pa, s, a->scan_tune), "scan");
-        hip_check(launch_scan(vb, d_start, nullptr, 1, sb, cnt(pb), pb, s, b->scan_tune), "scan");
+// ---- the host driver: q2_run = check, plan, bind, order, replay or enqueue, collect ----
+
+// a running offset rounded up to 256 bytes: the staging and scratch layouts
+struct Carve {
+    uint64_t off = 0;
+    uint64_t take(uint64_t bytes) {
+        const uint64_t o = off;
+        off += (bytes + 255) & ~255ull;
+        return o;
     }
-    *ra = pa;
-    *rb = pb;
+};
+
+constexpr uint32_t kMapKeys = 10000;  // supp_stock_map's keys (map_off: one more entry)
+
+// One call's sizes and layouts (q2_plan), then its buffers (q2_stage, q2_bind)
+struct Q2Plan {
+    // upper bounds (buffer sizes, grids): every SUPPLIER slot visited, every map entry looked up;
+    // launch shapes from the previous call's counts (the visited set depends on the data only)
+    uint64_t nslots, nchunks, n_max, m_max, n_hint, m_hint;
+    uint32_t nat_scan;  // NATION's scan size
+    bool fused_place;   // q2_place instead of q2_sel_start, q2_sel_place and q2_gather
+    // pinned call staging mirrored at the head of the device scratch: [map_off][read ids]
+    // [aborted] go down in one copy; [counts][aborted] come back in one copy; q_zero: the
+    // REGION / NATION scans' start key, 0 (:653, :734)
+    uint64_t q_map, q_rq, q_cn, q_ab, q_zero, q_end;
+    // the SUPPLIER table's scratch (REGION's and NATION's hold their scan rows)
+    uint64_t o_mir, o_pairs, o_sel, o_src, o_cnt, o_dst, o_keys, o_sbase, o_ik, o_ibase, o_rec, o_vis, o_rank, o_koff,
+        o_ccnt, o_kcnt, o_nv, scratch, reg_rows, nat_rows;
+    uint8_t *pq, *buf, *mir;  // the staging, the scratch, the staging's mirror in it
+    const uint32_t *d_map, *d_rq;
+    const uint64_t *d_zero;
+    uint64_t *d_counts, *d_sel, *d_src, *d_dst, *d_keys, *d_ik, *g_key;
+    int32_t *d_ab;
+    uint32_t *d_cnt, *ccnt, *kcnt, *g_koff, *g_nv;
+    stage_probe_out_dev *d_sbase, *d_ibase;
+    stage_q2_rec *d_rec;
+    int8_t *g_vis;
+    uint8_t *g_rank, *regs, *nats;  // regs / nats: the scans' first rows, each count (u32) 8 bytes before
+};
+
+// Everything q2_enqueue reads.  The struct is zeroed before it is filled (q2_run) and its bytes
+// are the graph key (q2_key): an argument cannot reach a launch without entering the key.
+struct Q2Launch {
+    Q2Plan p;
+    DevTable rv, nv, pv, iv, sv;  // REGION, NATION, SUPPLIER, ITEM, STOCK
+    ProbeTuning stock_tune, item_tune;
+    ScanTuning region_scan, nation_scan;
+    uint32_t supplier_kpad, item_kpad, stock_kpad;
+    const uint64_t *d_map_keys;
+    uint64_t name0, name1, mask0, mask1;  // regions[target] and its NUL as two masked words
+    uint32_t nq;
+    uint64_t max_out;
+    stage_q2_rec *host_out, *slot_out;  // the caller's page-locked records / the slot's device buffer
+    bool split;
+    hipStream_t s;
+};
+
+// the key of a call's captured graph: the launch arguments, and what the call depends on beyond
+// them -- the tables' own streams and scratch buffers
+std::string q2_key(const Q2Launch &L, std::initializer_list<const stage_table *> tables) {
+    std::string key;
+    key.reserve(sizeof L + tables.size() * (sizeof(hipStream_t) + sizeof(void *)));
+    key.append((const char *)&L, sizeof L);
+    for (const stage_table *t : tables) {
+        key.append((const char *)&t->dev.stream, sizeof t->dev.stream);
+        key.append((const char *)&t->dev.scratch.p, sizeof t->dev.scratch.p);
+    }
+    return key;
+}
+
+// everything up to the batch's one synchronisation, enqueued on L.s
+void q2_enqueue(const Q2Launch &L) {
+    const Q2Plan &p = L.p;
+    hipStream_t s = L.s;
+    hip_check(hipMemcpyAsync(p.mir, p.pq, p.q_end, hipMemcpyHostToDevice, s), "h2d");
+    // 1. the REGION / NATION scans (TableScanExecutor rows from key 0): one launch when
+    // launch_scan_pair takes them, else one each
+    auto cnt = [](uint8_t *rows) { return (uint32_t *)(rows - 8); };
+    if (scan_pair_supported(L.rv, kRegionScan, L.nv, p.nat_scan)) {
+        hip_check(launch_scan_pair(L.rv, p.d_zero, kRegionScan, cnt(p.regs), p.regs, L.nv, p.d_zero, p.nat_scan,
+                                   cnt(p.nats), p.nats, s),
+                  "scan pair");
+    } else {
+        hip_check(launch_scan(L.rv, p.d_zero, nullptr, 1, kRegionScan, cnt(p.regs), p.regs, s, L.region_scan), "scan");
+        hip_check(launch_scan(L.nv, p.d_zero, nullptr, 1, p.nat_scan, cnt(p.nats), p.nats, s, L.nation_scan), "scan");
+    }
+    // 2. the selection and the map segments, on the device (four kernels, no host wait)
+    if (p.nchunks) {
+        q2_sel_count<<<(unsigned)((p.nchunks + 3) / 4), 256, 0, s>>>(
+            p.regs, L.rv.stride, p.nats, L.nv.stride, L.name0, L.name1, L.mask0, L.mask1, L.pv, L.supplier_kpad,
+            p.nchunks, p.d_map, p.g_vis, p.g_rank, p.g_koff, p.g_key, p.ccnt, p.kcnt, p.g_nv);
+        if (p.fused_place) {  // starts, places and the STOCK keys in one launch
+            q2_place<<<(unsigned)((p.nchunks + 3) / 4), 1024, 0, s>>>(
+                p.ccnt, p.kcnt, p.nchunks, p.g_nv, p.g_vis, p.g_rank, p.g_koff, p.g_key, p.d_map, L.d_map_keys, p.m_max,
+                p.d_sel, p.d_src, p.d_cnt, p.d_dst, p.d_counts, p.d_keys);
+        } else {
+            q2_sel_start<<<1, 1024, 0, s>>>(p.ccnt, p.kcnt, p.nchunks, p.g_nv, p.d_counts);
+            q2_sel_place<<<(unsigned)((p.nslots + 255) / 256), 256, 0, s>>>(p.ccnt, p.kcnt, p.nslots, p.g_vis, p.g_rank,
+                                                                             p.g_koff, p.g_key, p.d_map, p.d_sel,
+                                                                             p.d_src, p.d_cnt, p.d_dst);
+        }
+    }
+    hip_check(hipGetLastError(), "select");
+    // 3. every visited supplier's STOCK keys, one probe of them all (the counts on the device)
+    if (!p.fused_place)
+        q2_gather<<<(unsigned)std::max<uint64_t>(std::min<uint64_t>(p.n_hint, 4096), 1), 256, 0, s>>>(
+            L.d_map_keys, p.d_src, p.d_dst, p.d_cnt, p.d_counts, p.m_max, p.d_keys);
+    // every query of the batch looks up the same STOCK keys (the visited suppliers and their
+    // supp_stock_map do not depend on the read id): each key is probed once, with no read id
+    // (the hit slot does not depend on it), and its visibility evaluated at every query's read
+    // id inside the per-supplier fold (launch_revisit_segments: the aborts and each
+    // supplier's last stock, per query)
+    // (the misses at every read id folded into the probe where its kernel takes them;
+    // q2_reduce re-evaluates each supplier's last lookup)
+    if (p.m_max && probe_missed_supported(L.sv)) {
+        hip_check(launch_probe_missed(L.sv, p.d_keys, p.m_max, p.d_sbase, s, L.stock_tune, p.d_counts + 1, p.m_hint,
+                                      p.d_rq, L.nq, p.d_ab),
+                  "stock probe");
+    } else if (p.m_max) {
+        hip_check(launch_probe(L.sv, p.d_keys, nullptr, nullptr, nullptr, p.m_max, p.d_sbase, nullptr, s, L.stock_tune,
+                               p.d_counts + 1, p.m_hint),
+                  "stock probe");
+        hip_check(launch_revisit_segments(L.sv, p.d_sbase, p.m_max, nullptr, nullptr, 0, p.d_rq, L.nq, nullptr, p.d_ab,
+                                          s, p.d_counts + 1, nullptr),
+                  "stock read ids");
+    }
+    q2_reduce<<<(unsigned)((p.n_max * L.nq + 255) / 256), 256, 0, s>>>(L.sv, p.d_sbase, p.d_rq, p.d_keys, p.d_dst,
+                                                                       p.d_cnt, p.d_sel, L.stock_kpad, p.d_counts, L.nq,
+                                                                       p.d_rec, p.d_ik);
+    // 4. item lookups of the last stocks (the same keys in every query: probed once, as above),
+    // the I_DATA filter, the records into `out`
+    hip_check(launch_probe(L.iv, p.d_ik, nullptr, nullptr, nullptr, p.n_max, p.d_ibase, nullptr, s, L.item_tune,
+                           p.d_counts, p.n_hint),
+              "item probe");
+    q2_finish<<<(unsigned)((p.n_max * L.nq + 255) / 256), 256, 0, s>>>(L.iv, p.d_ibase, p.d_rq, L.item_kpad, p.d_counts,
+                                                                       L.nq, p.d_rec, p.d_ab,
+                                                                       L.split ? nullptr : L.host_out, L.max_out,
+                                                                       L.slot_out, p.n_max);
+    hip_check(hipGetLastError(), "q2 kernels");
+    hip_check(hipMemcpyAsync(p.pq + p.q_cn, p.d_counts, 16 + L.nq * 4ull, hipMemcpyDeviceToHost, s), "d2h");
+}
+
+// STAGE_Q2_TRACE=1: host wall time of each phase on stderr
+struct Q2Trace {
+    static bool on() {
+        static const bool t = std::getenv("STAGE_Q2_TRACE") != nullptr;
+        return t;
+    }
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(const char *what) const {
+        if (on())
+            std::fprintf(stderr, "[q2] %s %.1f us\n", what,
+                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    }
+};
+
+// A hipGraph of an enqueue on one stream: captured on the second call in a row with the same key,
+// replayed while the key stays the same -- one launch instead of ~20 (STAGE_Q2_GRAPH=0: always
+// enqueue).  A capture or instantiation that fails is not tried again.  Returns what it did.
+template <class F>
+const char *replay_or_enqueue(Q2Graph &G, const std::string &key, hipStream_t s, F enqueue) {
+    static const bool graphs = [] {
+        const char *e = std::getenv("STAGE_Q2_GRAPH");
+        return !(e && std::strcmp(e, "0") == 0);
+    }();
+    const char *how = "enqueued";
+    bool launched = false;
+    if (graphs && !G.failed) {
+        if (G.exec && G.key == key) {
+            hip_check(hipGraphLaunch(G.exec, s), "q2 graph launch");
+            how = "replayed", launched = true;
+        } else if (G.last_key == key) {  // the same call twice: capture it
+            if (G.exec) (void)hipGraphExecDestroy(G.exec);
+            G.exec = nullptr;
+            G.key.clear();
+            hipGraph_t g = nullptr;
+            hip_check(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed), "q2 capture");
+            try {
+                enqueue();
+            } catch (...) {
+                (void)hipStreamEndCapture(s, &g);
+                if (g) (void)hipGraphDestroy(g);
+                (void)hipGetLastError();
+                throw;
+            }
+            hipError_t e = hipStreamEndCapture(s, &g);
+            if (!e) e = hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0);
+            if (g) (void)hipGraphDestroy(g);
+            if (e) {  // no graph for this call shape: enqueue as before from now on
+                (void)hipGetLastError();
+                G.exec = nullptr;
+                G.failed = true;
+                if (Q2Trace::on()) std::fprintf(stderr, "[q2] graph capture failed: %s\n", hipGetErrorString(e));
+            } else {
+                G.key = key;
+                hip_check(hipGraphLaunch(G.exec, s), "q2 graph launch");
+                how = "captured", launched = true;
+            }
+        }
+        G.last_key = key;
+    }
+    if (!launched) enqueue();
+    return how;
 }
 
 }  // namespace
 }  // namespace stage
 
+using namespace stage;
+
 // CH-Q2's users of the tables' per-call scratch, by table role (check_scratch_uses)
 enum { kRoleRegion, kRoleNation, kRoleSupplier, kRoleItem, kRoleStock };
-static const stage::ScratchUse kQ2Scratch[] = {{kRoleSupplier, "the CH-Q2 batch buffers"},
-                                               {kRoleRegion, "the REGION scan rows"},
-                                               {kRoleNation, "the NATION scan rows"},
-                                               {kRoleItem, "the stock-update staging"}};
+static const ScratchUse kQ2Scratch[] = {{kRoleSupplier, "the CH-Q2 batch buffers"},
+                                        {kRoleRegion, "the REGION scan rows"},
+                                        {kRoleNation, "the NATION scan rows"},
+                                        {kRoleItem, "the stock-update staging"}};
 constexpr int kQ2ScratchUses = (int)(sizeof(kQ2Scratch) / sizeof(kQ2Scratch[0]));
 
 // nq transactions at read ids rq[0..nq): out[q * max_out + k], aborted[q]; commit only for nq == 1
-static int q2_run(stage_table *region, stage_table *nation, stage_table *supplier, stage_table *item,
-                  stage_table *stock, const uint32_t *map_off, const uint64_t *d_map_keys, int32_t target_region,
-                  const uint32_t *rq, uint32_t nq, uint32_t commit_id, stage_q2_rec *out, uint64_t max_out,
-                  uint64_t *n_out, int32_t *aborted, void *stream, int slot = 0, bool async = false) {
-    for (stage_table *t : {region, nation, supplier, item, stock})
+struct Q2Call {
+    stage_table *region, *nation, *supplier, *item, *stock;
+    const uint32_t *map_off;
+    const uint64_t *d_map_keys;
+    int32_t target_region;
+    const uint32_t *rq;
+    uint32_t nq, commit_id;
+    stage_q2_rec *out;
+    uint64_t max_out, *n_out;
+    int32_t *aborted;
+    void *stream;
+    int slot;
+    bool async;
+};
+
+// the argument and state checks, in the order the CPU tests pin
+static int q2_check(const Q2Call &c) {
+    for (stage_table *t : {c.region, c.nation, c.supplier, c.item, c.stock})
         if (!t) return fail(STAGE_E_ARG, "null table");
     {
-        const void *roles[] = {region, nation, supplier, item, stock};
+        const void *roles[] = {c.region, c.nation, c.supplier, c.item, c.stock};
         int rc = guarded([&] {
-            stage::check_scratch_uses(kQ2Scratch, kQ2ScratchUses, roles);
+            check_scratch_uses(kQ2Scratch, kQ2ScratchUses, roles);
             return STAGE_OK;
         });
         if (rc) return rc;
     }
-    for (stage_table *t : {region, nation, supplier, item, stock}) {
+    for (stage_table *t : {c.region, c.nation, c.supplier, c.item, c.stock}) {
         int rc = need_synced(t);
         if (rc) return rc;
     }
-    if (!map_off || !d_map_keys || (!async && (!n_out || !aborted)) || (max_out && !out))
+    if (!c.map_off || !c.d_map_keys || (!c.async && (!c.n_out || !c.aborted)) || (c.max_out && !c.out))
         return fail(STAGE_E_ARG, "null argument");
-    if (slot < 0 || slot > 1) return fail(STAGE_E_ARG, "slot must be 0 or 1");
-    if (stock->q2p[slot].active) return fail(STAGE_E_STATE, "CH-Q2 slot still in flight: stage_ch_query2_wait first");
-    if (target_region < 0 || target_region > 4) return fail(STAGE_E_ARG, "target_region must be 0..4");
-    for (stage_table *t : {region, nation, supplier, item})
+    if (c.slot < 0 || c.slot > 1) return fail(STAGE_E_ARG, "slot must be 0 or 1");
+    if (c.stock->q2p[c.slot].active)
+        return fail(STAGE_E_STATE, "CH-Q2 slot still in flight: stage_ch_query2_wait first");
+    if (c.target_region < 0 || c.target_region > 4) return fail(STAGE_E_ARG, "target_region must be 0..4");
+    for (stage_table *t : {c.region, c.nation, c.supplier, c.item})
         if (facts(t).params().key_width != 8) return fail(STAGE_E_ARG, "REGION/NATION/SUPPLIER/ITEM keys are 8 bytes");
-    if (facts(stock).params().key_width != 16) return fail(STAGE_E_ARG, "STOCK keys are {w, i}: 16 bytes");
-    if (facts(region).params().payload_size < 55 || facts(nation).params().payload_size < 8 ||
-        facts(supplier).params().payload_size < 8 || facts(item).params().payload_size < stage::kIDataOff + 64 ||
-        facts(stock).params().payload_size < 16)
+    if (facts(c.stock).params().key_width != 16) return fail(STAGE_E_ARG, "STOCK keys are {w, i}: 16 bytes");
+    if (facts(c.region).params().payload_size < 55 || facts(c.nation).params().payload_size < 8 ||
+        facts(c.supplier).params().payload_size < 8 || facts(c.item).params().payload_size < kIDataOff + 64 ||
+        facts(c.stock).params().payload_size < 16)
         return fail(STAGE_E_ARG, "payloads too short for the Q2 columns");
-    for (stage_table *t : {region, nation, supplier, item})
-        if (t->dev.device != stock->dev.device) return fail(STAGE_E_ARG, "tables on different devices");
-    return guarded([&] {
-        using namespace stage;
-        hip_check(hipSetDevice(stock->dev.device), "hipSetDevice");
-        hipStream_t s = pick(stock, stream);
-        // STAGE_Q2_TRACE=1: host wall time of each phase on stderr
-        static const bool trace = std::getenv("STAGE_Q2_TRACE") != nullptr;
-        const auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char *what) {
-            if (trace)
-                std::fprintf(stderr, "[q2] %s %.1f us\n", what,
-                             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-        };
-        if (!async) {
-            *n_out = 0;
-            for (uint32_t q = 0; q < nq; ++q) aborted[q] = 0;
-        }
-        const DevTable &pv = supplier->dev.view, &sv = stock->dev.view, &iv = item->dev.view;
-        const uint64_t nslots = (uint64_t)pv.nleaves * pv.cap;
-        if (pv.cap % 64) return fail(STAGE_E_UNSUPPORTED, "SUPPLIER leaves of a multiple of 64 slots");
-        const uint64_t nchunks = nslots / 64;
-        // upper bounds (buffer sizes, grids): every SUPPLIER slot visited, every map entry looked up
-        constexpr uint32_t kMapKeys = 10000;
-        uint64_t m_max = 0;
-        for (uint32_t k = 0; k < kMapKeys; ++k) m_max += map_off[k + 1] > map_off[k] ? map_off[k + 1] - map_off[k] : 0;
-        const uint64_t n_max = std::max<uint64_t>(nslots, 1);
-        // launch shapes from the previous call's counts (the visited set depends on the data only)
-        const uint64_t n_hint = stock->q2_hint[0] ? std::min(stock->q2_hint[0], n_max) : n_max;
-        const uint64_t m_hint = stock->q2_hint[1] ? std::min(stock->q2_hint[1], std::max<uint64_t>(m_max, 1)) : m_max;
-        // q2_place up to kPlaceChunks SUPPLIER chunks (STAGE_Q2_PLACE_CHUNKS: another limit, for
-        // the tests of the three-kernel form larger tables take)
-        const char *pe = std::getenv("STAGE_Q2_PLACE_CHUNKS");
-        const bool fused_place = nchunks <= (pe ? std::strtoull(pe, nullptr, 10) : kPlaceChunks);
-        // pinned call staging mirrored at the head of the device scratch: [map_off][read ids]
-        // [aborted] go down in one copy; [counts][aborted] come back in one copy
-        auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
-        const uint64_t q_map = 0, q_rq = q_map + al((kMapKeys + 1) * 4ull), q_cn = q_rq + al(nq * 4ull),
-                       q_ab = q_cn + 16, q_zero = q_ab + al(nq * 4ull), q_end = q_zero + 16;
-        uint8_t *pq = pinned_bytes(stock->dev, q_end, kQ2Pinned + slot);
-        std::memcpy(pq + q_map, map_off, (kMapKeys + 1) * 4ull);
-        std::memcpy(pq + q_rq, rq, nq * 4ull);
-        std::memset(pq + q_cn, 0, 16 + nq * 4ull);
-        std::memset(pq + q_zero, 0, 16);  // the REGION / NATION scans' start key: 0 (:653, :734)
-        lap("staged");
-        uint64_t off = 0;
-        auto take = [&](uint64_t bytes) {
-            const uint64_t o = off;
-            off += al(bytes);
-            return o;
-        };
-        const uint64_t o_mir = take(q_end), o_pairs = take(n_max * 16), o_sel = take(n_max * 8),
-                       o_src = take(n_max * 8), o_cnt = take(n_max * 4), o_dst = take(n_max * 8),
-                       o_keys = take(std::max<uint64_t>(m_max, 1) * 16), o_sbase = take(std::max<uint64_t>(m_max, 1) * 32),
-                       o_ik = take(n_max * 8 * nq),
-                       o_ibase = take(n_max * 32), o_rec = take(n_max * nq * sizeof(stage_q2_rec)),
-                       o_vis = take(n_max), o_rank = take(n_max), o_koff = take(n_max * 4),
-                       o_ccnt = take(std::max<uint64_t>(nchunks, 1) * kVisits * 4),
-                       o_kcnt = take(std::max<uint64_t>(nchunks, 1) * kVisits * 4), o_nv = take(4);
-        // NATION's scan (scan_sz 65) is past the compact scan kernel's 63 records; a table of fewer
-        // slots than that returns the same records for every scan size of at least its slot count
-        // (the scan ends at the table's end), so such a table is scanned with that size instead
-        uint32_t nat_scan = kNationScan;
-        if (nation->dev.view.nleaves <= 4) {
-            uint64_t slots = 0;
-            for (const auto &L : host(nation).leaves_)
-                if (L.live) slots += L.count;
-            if (slots < (uint64_t)kNationScan) nat_scan = (uint32_t)std::max<uint64_t>(slots, 1);
-        }
-        // a batch still in flight uses these scratch buffers: growing one (a reallocation) waits
-        // for it first
-        const uint64_t reg_rows = 64 + (uint64_t)kRegionScan * region->dev.view.stride,
-                       nat_rows = 64 + (uint64_t)kNationScan * nation->dev.view.stride;
-        if ((stock->q2p[0].active || stock->q2p[1].active) &&
-            (supplier->dev.scratch.cap < off || region->dev.scratch.cap < reg_rows || nation->dev.scratch.cap < nat_rows))
-            hip_check(hipDeviceSynchronize(), "q2 drain");
-        // the SUPPLIER table's scratch: REGION's and NATION's hold their scan rows (scan_dims)
-        uint8_t *buf = scratch_bytes(supplier->dev, off), *mir = buf + o_mir;
-        auto *d_map = (const uint32_t *)(mir + q_map);
-        auto *d_rq = (const uint32_t *)(mir + q_rq);
-        auto *d_counts = (uint64_t *)(mir + q_cn);
-        auto *d_ab = (int32_t *)(mir + q_ab);
-        auto *d_sel = (uint64_t *)(buf + o_sel);
-        auto *d_src = (uint64_t *)(buf + o_src), *d_dst = (uint64_t *)(buf + o_dst);
-        auto *d_cnt = (uint32_t *)(buf + o_cnt);
-        auto *d_keys = (uint64_t *)(buf + o_keys), *d_ik = (uint64_t *)(buf + o_ik);
-        auto *d_sbase = (stage_probe_out_dev *)(buf + o_sbase), *d_ibase = (stage_probe_out_dev *)(buf + o_ibase);
-        auto *d_rec = (stage_q2_rec *)(buf + o_rec);
-        char tname[16] = {0};
-        std::strncpy(tname, kRegions[target_region], 15);
-        uint64_t name0, name1, mask0 = 0, mask1 = 0;
-        std::memcpy(&name0, tname, 8);
-        std::memcpy(&name1, tname + 8, 8);
-        for (size_t b = 0; b <= std::strlen(tname); ++b)  // the name and its NUL
-            (b < 8 ? mask0 : mask1) |= 0xFFull << (8 * (b % 8));
-        auto *g_key = (uint64_t *)(buf + o_pairs);
-        auto *g_vis = (int8_t *)(buf + o_vis);
-        auto *g_rank = (uint8_t *)(buf + o_rank);
-        auto *ccnt = (uint32_t *)(buf + o_ccnt), *kcnt = (uint32_t *)(buf + o_kcnt);
-        auto *g_koff = (uint32_t *)(buf + o_koff);
-        auto *g_nv = (uint32_t *)(buf + o_nv);
-        // `out` in page-locked memory (stage_host_alloc, stage.pinned_empty): the finishing kernel
-        // writes the records into it directly; otherwise they are copied once the count is known
-        stage_q2_rec *host_out = nullptr;
-        if (out && max_out) {  // page-locked memory has a device view; pageable memory has none
-            void *dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, out, 0) == hipSuccess && dp) host_out = (stage_q2_rec *)dp;
-            (void)hipGetLastError();  // a pageable pointer is not an error here
-        }
-        if (trace) std::fprintf(stderr, "[q2] out %s\n", host_out ? "page-locked: written by q2_finish" : "pageable: copied");
-        if (async && out && max_out && !host_out)
-            return fail(STAGE_E_ARG, "stage_ch_query2_batch_async needs a page-locked out (stage_host_alloc)");
-        // an async batch's records leave from the side stream (Q2Pending::split): finished into
-        // the slot's own device buffer, row pitch n_max
-        Q2Pending &P = stock->q2p[slot];
-        const bool split = async && host_out;
-        stage_q2_rec *slot_out = nullptr;
-        if (split) {
-            const uint64_t need = n_max * nq * sizeof(stage_q2_rec);
-            if (P.dcap < need) {  // the slot is idle (checked above): its old buffer is unused
-                if (P.dbuf) hip_check(hipFree(P.dbuf), "q2 slot buffer");
-                P.dbuf = nullptr;
-                P.dcap = 0;
-                hip_check(hipMalloc(&P.dbuf, need), "q2 slot buffer");
-                P.dcap = need;
-            }
-            if (!stock->q2_side) hip_check(hipStreamCreateWithFlags(&stock->q2_side, hipStreamNonBlocking), "q2 side stream");
-            if (!P.fin) hip_check(hipEventCreateWithFlags(&P.fin, hipEventDisableTiming), "q2 event");
-            slot_out = (stage_q2_rec *)P.dbuf;
-        }
-        lap("buffers");
-        // the scan rows' scratch sized before any capture (scan_dims asks for the same size again)
-        (void)scratch_bytes(region->dev, reg_rows);
-        (void)scratch_bytes(nation->dev, nat_rows);
-        // work a caller left on the REGION / NATION tables' own streams (a call without a stream
-        // runs there) is finished first: the whole batch then goes on s.  (Round 5 forked the two
-        // scans onto those streams and joined them back: the cross-stream waits cost ~20 µs of
-        // the ~35 µs the scans took, against ~10 µs for the two scans back to back on s.)
-        for (stage_table *d : {region, nation})
-            if (d->dev.stream && d->dev.stream != s) hip_check(hipStreamSynchronize(d->dev.stream), "dimension stream");
-        // both slots share the SUPPLIER scratch and the REGION / NATION scan rows: a batch still in
-        // flight on another stream is waited for on the device before this one is enqueued (on its
-        // own stream, stream order already keeps them apart)
-        for (const Q2Pending &o : stock->q2p)  // (a split batch's kernels: its copy reads only its slot buffer)
-            if (o.active && o.stream != s) hip_check(hipStreamWaitEvent(s, o.split ? o.fin : o.ev, 0), "q2 other slot");
-        // everything up to the batch's one synchronisation, enqueued on s
-        auto enqueue = [&] {
-            hip_check(hipMemcpyAsync(mir, pq, q_end, hipMemcpyHostToDevice, s), "h2d");
-            // 1. the REGION / NATION scans
-            const auto *d_zero = (const uint64_t *)(mir + q_zero);
-            const uint8_t *regs = nullptr, *nats = nullptr;
-            scan_dims(region, kRegionScan, nation, nat_scan, d_zero, s, &regs, &nats);
-            // 2. the selection and the map segments, on the device (four kernels, no host wait)
-            if (nchunks) {
-                q2_sel_count<<<(unsigned)((nchunks + 3) / 4), 256, 0, s>>>(
-                    regs, region->dev.view.stride, nats, nation->dev.view.stride, name0, name1, mask0, mask1, pv,
-                    facts(supplier).key_pad(), nchunks, d_map, g_vis, g_rank, g_koff, g_key, ccnt, kcnt, g_nv);
-                if (fused_place) {  // starts, places and the STOCK keys in one launch
-                    q2_place<<<(unsigned)((nchunks + 3) / 4), 1024, 0, s>>>(ccnt, kcnt, nchunks, g_nv, g_vis, g_rank,
-                                                                          g_koff, g_key, d_map, d_map_keys, m_max,
-                                                                          d_sel, d_src, d_cnt, d_dst, d_counts, d_keys);
-                } else {
-                    q2_sel_start<<<1, 1024, 0, s>>>(ccnt, kcnt, nchunks, g_nv, d_counts);
-                    q2_sel_place<<<(unsigned)((nslots + 255) / 256), 256, 0, s>>>(ccnt, kcnt, nslots, g_vis, g_rank,
-                                                                                   g_koff, g_key, d_map, d_sel, d_src,
-                                                                                   d_cnt, d_dst);
-                }
-            }
-            hip_check(hipGetLastError(), "select");
-            // 3. every visited supplier's STOCK keys, one probe of them all (the counts on the device)
-            if (!fused_place)
-                q2_gather<<<(unsigned)std::max<uint64_t>(std::min<uint64_t>(n_hint, 4096), 1), 256, 0, s>>>(
-                    d_map_keys, d_src, d_dst, d_cnt, d_counts, m_max, d_keys);
+    for (stage_table *t : {c.region, c.nation, c.supplier, c.item})
+        if (t->dev.device != c.stock->dev.device) return fail(STAGE_E_ARG, "tables on different devices");
+    return STAGE_OK;
+}
 
-            // every query of the batch looks up the same STOCK keys (the visited suppliers and their
-            // supp_stock_map do not depend on the read id): each key is probed once, with no read id
-            // (the hit slot does not depend on it), and its visibility evaluated at every query's read
-            // id inside the per-supplier fold (launch_revisit_segments: the aborts and each
-            // supplier's last stock, per query)
-            // (the misses at every read id folded into the probe where its kernel takes them;
-            // q2_reduce re-evaluates each supplier's last lookup)
-            if (m_max && probe_missed_supported(sv)) {
-                hip_check(launch_probe_missed(sv, d_keys, m_max, d_sbase, s, stock->tune, d_counts + 1, m_hint, d_rq, nq,
-                                              d_ab),
-                          "stock probe");
-            } else if (m_max) {
-                hip_check(launch_probe(sv, d_keys, nullptr, nullptr, nullptr, m_max, d_sbase, nullptr, s, stock->tune,
-                                       d_counts + 1, m_hint),
-                          "stock probe");
-                hip_check(launch_revisit_segments(sv, d_sbase, m_max, nullptr, nullptr, 0, d_rq, nq, nullptr, d_ab, s,
-                                                  d_counts + 1, nullptr),
-                          "stock read ids");
-            }
-            q2_reduce<<<(unsigned)((n_max * nq + 255) / 256), 256, 0, s>>>(sv, d_sbase, d_rq, d_keys, d_dst, d_cnt, d_sel,
-                                                                           facts(stock).key_pad(), d_counts, nq, d_rec,
-                                                                           d_ik);
-            // 4. item lookups of the last stocks (the same keys in every query: probed once, as above),
-            // the I_DATA filter, the records into `out`
-            hip_check(launch_probe(iv, d_ik, nullptr, nullptr, nullptr, n_max, d_ibase, nullptr, s, item->tune, d_counts,
-                                   n_hint),
-                      "item probe");
-            q2_finish<<<(unsigned)((n_max * nq + 255) / 256), 256, 0, s>>>(iv, d_ibase, d_rq, facts(item).key_pad(),
-                                                                           d_counts, nq, d_rec, d_ab,
-                                                                           split ? nullptr : host_out, max_out,
-                                                                           slot_out, n_max);
-            hip_check(hipGetLastError(), "q2 kernels");
-            hip_check(hipMemcpyAsync(pq + q_cn, d_counts, 16 + nq * 4ull, hipMemcpyDeviceToHost, s), "d2h");
-        };
-        // A hipGraph of the enqueue: captured on the second call with the same arguments (every
-        // kernel argument, buffer, stream and launch shape is in the key), replayed while they
-        // stay the same -- one launch instead of ~20 (STAGE_Q2_GRAPH=0: always enqueue)
-        static const bool graphs = [] {
-            const char *e = std::getenv("STAGE_Q2_GRAPH");
-            return !(e && std::strcmp(e, "0") == 0);
-        }();
-        std::string key;
-        auto put = [&key](const void *p, size_t n) { key.append((const char *)p, n); };
-        auto putv = [&](auto v) { put(&v, sizeof v); };
-        for (stage_table *t : {region, nation, supplier, item, stock}) {
-            put(&t->dev.view, sizeof t->dev.view);
-            putv(t->dev.stream);
-            putv(t->dev.scratch.p);
+// the call's sizes and the byte layouts of its staging and scratch
+static void q2_plan(Q2Plan &p, const Q2Call &c) {
+    const DevTable &pv = c.supplier->dev.view;
+    p.nslots = (uint64_t)pv.nleaves * pv.cap;
+    p.nchunks = p.nslots / 64;
+    p.m_max = 0;
+    for (uint32_t k = 0; k < kMapKeys; ++k)
+        p.m_max += c.map_off[k + 1] > c.map_off[k] ? c.map_off[k + 1] - c.map_off[k] : 0;
+    p.n_max = std::max<uint64_t>(p.nslots, 1);
+    const uint64_t m1 = std::max<uint64_t>(p.m_max, 1), c1 = std::max<uint64_t>(p.nchunks, 1), *hint = c.stock->q2_hint;
+    p.n_hint = hint[0] ? std::min(hint[0], p.n_max) : p.n_max;
+    p.m_hint = hint[1] ? std::min(hint[1], m1) : p.m_max;
+    // q2_place up to kPlaceChunks SUPPLIER chunks (STAGE_Q2_PLACE_CHUNKS: another limit, for
+    // the tests of the three-kernel form larger tables take)
+    const char *pe = std::getenv("STAGE_Q2_PLACE_CHUNKS");
+    p.fused_place = p.nchunks <= (pe ? std::strtoull(pe, nullptr, 10) : kPlaceChunks);
+    Carve q;
+    p.q_map = q.take((kMapKeys + 1) * 4ull), p.q_rq = q.take(c.nq * 4ull);
+    p.q_cn = q.off, q.off += 16;  // the 16 bytes of counts, the flags right behind them
+    p.q_ab = q.take(c.nq * 4ull), p.q_zero = q.off, p.q_end = p.q_zero + 16;
+    Carve o;
+    p.o_mir = o.take(p.q_end), p.o_pairs = o.take(p.n_max * 16), p.o_sel = o.take(p.n_max * 8);
+    p.o_src = o.take(p.n_max * 8), p.o_cnt = o.take(p.n_max * 4), p.o_dst = o.take(p.n_max * 8);
+    p.o_keys = o.take(m1 * 16), p.o_sbase = o.take(m1 * 32), p.o_ik = o.take(p.n_max * 8 * c.nq);
+    p.o_ibase = o.take(p.n_max * 32), p.o_rec = o.take(p.n_max * c.nq * sizeof(stage_q2_rec));
+    p.o_vis = o.take(p.n_max), p.o_rank = o.take(p.n_max), p.o_koff = o.take(p.n_max * 4);
+    p.o_ccnt = o.take(c1 * kVisits * 4), p.o_kcnt = o.take(c1 * kVisits * 4), p.o_nv = o.take(4);
+    p.scratch = o.off;
+    // NATION's scan (scan_sz 65) is past the compact scan kernel's 63 records; a table of fewer
+    // slots than that returns the same records for every scan size of at least its slot count
+    // (the scan ends at the table's end), so such a table is scanned with that size instead
+    p.nat_scan = kNationScan;
+    if (c.nation->dev.view.nleaves <= 4) {
+        uint64_t slots = 0;
+        for (const auto &L : host(c.nation).leaves_)
+            if (L.live) slots += L.count;
+        if (slots < (uint64_t)kNationScan) p.nat_scan = (uint32_t)std::max<uint64_t>(slots, 1);
+    }
+    p.reg_rows = 64 + (uint64_t)kRegionScan * c.region->dev.view.stride;
+    p.nat_rows = 64 + (uint64_t)kNationScan * c.nation->dev.view.stride;
+}
+
+// the slot's pinned staging, filled
+static void q2_stage(Q2Plan &p, const Q2Call &c) {
+    p.pq = pinned_bytes(c.stock->dev, p.q_end, kQ2Pinned + c.slot);
+    std::memcpy(p.pq + p.q_map, c.map_off, (kMapKeys + 1) * 4ull);
+    std::memcpy(p.pq + p.q_rq, c.rq, c.nq * 4ull);
+    std::memset(p.pq + p.q_cn, 0, 16 + c.nq * 4ull);
+    std::memset(p.pq + p.q_zero, 0, 16);
+}
+
+// the device buffers: the batch buffers in SUPPLIER's scratch, the scan rows in REGION's and
+// NATION's -- all sized here, before any capture
+static void q2_bind(Q2Plan &p, const Q2Call &c) {
+    // a batch still in flight uses these scratch buffers: growing one (a reallocation) waits
+    // for it first
+    if ((c.stock->q2p[0].active || c.stock->q2p[1].active) &&
+        (c.supplier->dev.scratch.cap < p.scratch || c.region->dev.scratch.cap < p.reg_rows ||
+         c.nation->dev.scratch.cap < p.nat_rows))
+        hip_check(hipDeviceSynchronize(), "q2 drain");
+    uint8_t *buf = p.buf = scratch_bytes(c.supplier->dev, p.scratch), *mir = p.mir = buf + p.o_mir;
+    p.d_map = (const uint32_t *)(mir + p.q_map), p.d_rq = (const uint32_t *)(mir + p.q_rq);
+    p.d_counts = (uint64_t *)(mir + p.q_cn), p.d_ab = (int32_t *)(mir + p.q_ab);
+    p.d_zero = (const uint64_t *)(mir + p.q_zero);
+    p.g_key = (uint64_t *)(buf + p.o_pairs), p.d_sel = (uint64_t *)(buf + p.o_sel);
+    p.d_src = (uint64_t *)(buf + p.o_src), p.d_cnt = (uint32_t *)(buf + p.o_cnt), p.d_dst = (uint64_t *)(buf + p.o_dst);
+    p.d_keys = (uint64_t *)(buf + p.o_keys), p.d_sbase = (stage_probe_out_dev *)(buf + p.o_sbase);
+    p.d_ik = (uint64_t *)(buf + p.o_ik), p.d_ibase = (stage_probe_out_dev *)(buf + p.o_ibase);
+    p.d_rec = (stage_q2_rec *)(buf + p.o_rec);
+    p.g_vis = (int8_t *)(buf + p.o_vis), p.g_rank = buf + p.o_rank, p.g_koff = (uint32_t *)(buf + p.o_koff);
+    p.ccnt = (uint32_t *)(buf + p.o_ccnt), p.kcnt = (uint32_t *)(buf + p.o_kcnt), p.g_nv = (uint32_t *)(buf + p.o_nv);
+    p.regs = scratch_bytes(c.region->dev, p.reg_rows) + 64;
+    p.nats = scratch_bytes(c.nation->dev, p.nat_rows) + 64;
+}
+
+// `out` in page-locked memory (stage_host_alloc, stage.pinned_empty) has a device view: the
+// finishing kernel writes the records into it directly.  Pageable memory has none (null): the
+// records are copied once the count is known.
+static stage_q2_rec *q2_device_view(stage_q2_rec *out, uint64_t max_out) {
+    void *dp = nullptr;
+    if (!out || !max_out) return nullptr;
+    if (hipHostGetDevicePointer(&dp, out, 0) != hipSuccess) dp = nullptr;
+    (void)hipGetLastError();  // a pageable pointer is not an error here
+    return (stage_q2_rec *)dp;
+}
+
+// an async batch's records leave from the side stream (Q2Pending::split): finished into the
+// slot's own device buffer of `need` bytes, row pitch n_max
+static stage_q2_rec *q2_slot_buffer(stage_table *stock, Q2Pending &P, uint64_t need) {
+    if (P.dcap < need) {  // the slot is idle (q2_check): its old buffer is unused
+        if (P.dbuf) hip_check(hipFree(P.dbuf), "q2 slot buffer");
+        P.dbuf = nullptr;
+        P.dcap = 0;
+        hip_check(hipMalloc(&P.dbuf, need), "q2 slot buffer");
+        P.dcap = need;
+    }
+    if (!stock->q2_side) hip_check(hipStreamCreateWithFlags(&stock->q2_side, hipStreamNonBlocking), "q2 side stream");
+    if (!P.fin) hip_check(hipEventCreateWithFlags(&P.fin, hipEventDisableTiming), "q2 event");
+    return (stage_q2_rec *)P.dbuf;
+}
+
+// the launch arguments beyond the plan
+static void q2_arguments(Q2Launch &L, const Q2Call &c, stage_q2_rec *host_out, stage_q2_rec *slot_out, hipStream_t s) {
+    L.rv = c.region->dev.view, L.nv = c.nation->dev.view, L.pv = c.supplier->dev.view;
+    L.iv = c.item->dev.view, L.sv = c.stock->dev.view;
+    L.stock_tune = c.stock->tune, L.item_tune = c.item->tune;
+    L.region_scan = c.region->scan_tune, L.nation_scan = c.nation->scan_tune;
+    L.supplier_kpad = facts(c.supplier).key_pad(), L.item_kpad = facts(c.item).key_pad();
+    L.stock_kpad = facts(c.stock).key_pad();
+    L.d_map_keys = c.d_map_keys;
+    char tname[16] = {0};
+    std::strncpy(tname, kRegions[c.target_region], 15);
+    std::memcpy(&L.name0, tname, 8);
+    std::memcpy(&L.name1, tname + 8, 8);
+    for (size_t b = 0; b <= std::strlen(tname); ++b)  // the name and its NUL
+        (b < 8 ? L.mask0 : L.mask1) |= 0xFFull << (8 * (b % 8));
+    L.nq = c.nq, L.max_out = c.max_out, L.host_out = host_out, L.slot_out = slot_out;
+    L.split = slot_out != nullptr;
+    L.s = s;
+}
+
+// what must be over before the batch starts on s
+static void q2_order(const Q2Call &c, hipStream_t s) {
+    // work a caller left on the REGION / NATION tables' own streams (a call without a stream
+    // runs there) is finished first: the whole batch then goes on s.  (Round 5 forked the two
+    // scans onto those streams and joined them back: the cross-stream waits cost ~20 µs of
+    // the ~35 µs the scans took, against ~10 µs for the two scans back to back on s.)
+    for (stage_table *d : {c.region, c.nation})
+        if (d->dev.stream && d->dev.stream != s) hip_check(hipStreamSynchronize(d->dev.stream), "dimension stream");
+    // both slots share the SUPPLIER scratch and the REGION / NATION scan rows: a batch still in
+    // flight on another stream is waited for on the device before this one is enqueued (on its
+    // own stream, stream order already keeps them apart)
+    for (const Q2Pending &o : c.stock->q2p)  // (a split batch's kernels: its copy reads only its slot buffer)
+        if (o.active && o.stream != s) hip_check(hipStreamWaitEvent(s, o.split ? o.fin : o.ev, 0), "q2 other slot");
+}
+
+// where the enqueued batch's results will be (q2_collect); an async batch's events and, when
+// split, its records' copy on the side stream
+static void q2_park(const Q2Call &c, const Q2Launch &L, Q2Pending &P) {
+    const Q2Plan &p = L.p;
+    P.pq = p.pq, P.q_cn = p.q_cn, P.q_ab = p.q_ab, P.nq = c.nq, P.n_max = p.n_max, P.m_max = p.m_max;
+    P.stream = L.s, P.split = L.split, P.out = c.out, P.max_out = c.max_out, P.slot_out = L.slot_out, P.cols = 0;
+    if (!c.async) return;
+    if (!P.ev) hip_check(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming), "q2 event");
+    if (P.split) {  // the records cross PCIe from the side stream while s goes on
+        hip_check(hipEventRecord(P.fin, L.s), "q2 event");
+        hip_check(hipStreamWaitEvent(c.stock->q2_side, P.fin, 0), "q2 side wait");
+        // a 2-D copy (the DMA engine) of the expected count's columns -- the last call's
+        // count; q2_collect copies any more.  (A kernel writing the records over PCIe from the
+        // side stream slowed the next batch's kernels beside it ~4x, 0.153 ms a batch
+        // against 0.127 with the copy, r06q2emit.)
+        P.cols = std::min(p.n_hint, c.max_out);
+        if (P.cols)
+            hip_check(hipMemcpy2DAsync(c.out, c.max_out * sizeof(stage_q2_rec), L.slot_out,
+                                       p.n_max * sizeof(stage_q2_rec), P.cols * sizeof(stage_q2_rec), c.nq,
+                                       hipMemcpyDeviceToHost, c.stock->q2_side),
+                      "q2 records copy");
+        hip_check(hipEventRecord(P.ev, c.stock->q2_side), "q2 event");
+    } else {
+        hip_check(hipEventRecord(P.ev, L.s), "q2 event");
+    }
+    P.active = true;
+}
+
+// A finished batch's results (after the stream or event synchronisation): the counts and aborted
+// flags out of its staging, the rest of a split emit; returns the number of visited suppliers
+static uint64_t q2_collect(stage_table *stock, const Q2Pending &P, uint64_t *n_out, int32_t *aborted) {
+    uint64_t cn[2];
+    std::memcpy(cn, P.pq + P.q_cn, 16);
+    std::memcpy(aborted, P.pq + P.q_ab, 4ull * P.nq);
+    if (cn[0] > P.n_max || cn[1] > P.m_max) throw std::runtime_error("q2: device counts out of range");
+    const uint64_t want = std::min<uint64_t>(cn[0], P.max_out);
+    if (P.split && want > P.cols)  // more records than the copy expected
+        hip_check(hipMemcpy2D(P.out + P.cols, P.max_out * sizeof(stage_q2_rec), P.slot_out + P.cols,
+                              P.n_max * sizeof(stage_q2_rec), (want - P.cols) * sizeof(stage_q2_rec), P.nq,
+                              hipMemcpyDeviceToHost),
+                  "q2 records rest");
+    stock->q2_hint[0] = cn[0];
+    stock->q2_hint[1] = cn[1];
+    *n_out = cn[0];
+    if (cn[0] == 0)
+        for (uint32_t q = 0; q < P.nq; ++q) aborted[q] = 0;
+    return cn[0];
+}
+
+// 5. the transaction's stock updates (the marked ones of recs[0..n)), through the device write
+// path; each one's code into its record
+static int q2_apply_updates(const Q2Call &c, hipStream_t s, stage_q2_rec *recs, uint64_t n) {
+    std::vector<uint64_t> uk;
+    std::vector<int32_t> ud;
+    std::vector<uint32_t> ui;
+    for (uint32_t k = 0; k < n; ++k)
+        if (recs[k].update) {
+            uk.push_back((uint64_t)recs[k].s_w_id);
+            uk.push_back((uint64_t)recs[k].s_i_id);
+            ud.insert(ud.end(), {recs[k].s_quantity + 50, recs[k].s_ytd, recs[k].s_order_cnt, recs[k].s_remote_cnt});
+            ui.push_back(k);
         }
-        put(&stock->tune, sizeof stock->tune);
-        put(&item->tune, sizeof item->tune);
-        put(&region->scan_tune, sizeof region->scan_tune);
-        put(&nation->scan_tune, sizeof nation->scan_tune);
-        for (uint64_t v : {(uint64_t)(uintptr_t)d_map_keys, (uint64_t)target_region, (uint64_t)nq, max_out,
-                           (uint64_t)(uintptr_t)host_out, (uint64_t)(uintptr_t)pq, (uint64_t)(uintptr_t)buf, q_end,
-                           n_max, m_max, n_hint, m_hint, (uint64_t)(uintptr_t)s, (uint64_t)nat_scan,
-                           (uint64_t)(uintptr_t)slot_out, (uint64_t)fused_place})
-            putv(v);
-        lap("key");
-        Q2Graph &G = stock->q2g[slot];
-        bool launched = false;
-        if (graphs && !G.failed) {
-            if (G.exec && G.key == key) {
-                hip_check(hipGraphLaunch(G.exec, s), "q2 graph launch");
-                launched = true;
-            } else if (G.last_key == key) {  // the same call twice: capture it
-                if (G.exec) (void)hipGraphExecDestroy(G.exec);
-                G.exec = nullptr;
-                G.key.clear();
-                hipGraph_t g = nullptr;
-                hip_check(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed), "q2 capture");
-                try {
-                    enqueue();
-                } catch (...) {
-                    (void)hipStreamEndCapture(s, &g);
-                    if (g) (void)hipGraphDestroy(g);
-                    (void)hipGetLastError();
-                    throw;
-                }
-                hipError_t e = hipStreamEndCapture(s, &g);
-                if (!e) e = hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0);
-                if (g) (void)hipGraphDestroy(g);
-                if (e) {  // no graph for this call shape: enqueue as before from now on
-                    (void)hipGetLastError();
-                    G.exec = nullptr;
-                    G.failed = true;
-                    if (trace) std::fprintf(stderr, "[q2] graph capture failed: %s\n", hipGetErrorString(e));
-                } else {
-                    G.key = key;
-                    hip_check(hipGraphLaunch(G.exec, s), "q2 graph launch");
-                    launched = true;
-                }
-            }
-            G.last_key = key;
+    const uint64_t nu = ui.size();
+    if (!nu) return STAGE_OK;
+    Carve u;
+    const uint64_t u_k = u.take(nu * 16), u_d = u.take(nu * 16), u_w = u.take(nu * 4), u_c = u.take(nu * 4),
+                   u_rc = u.take(nu);
+    uint8_t *ub = scratch_bytes(c.item->dev, u.off);
+    std::vector<uint32_t> wid(nu, c.rq[0]), cid(nu, c.commit_id);
+    hip_check(hipMemcpyAsync(ub + u_k, uk.data(), nu * 16, hipMemcpyHostToDevice, s), "h2d");
+    hip_check(hipMemcpyAsync(ub + u_d, ud.data(), nu * 16, hipMemcpyHostToDevice, s), "h2d");
+    hip_check(hipMemcpyAsync(ub + u_w, wid.data(), nu * 4, hipMemcpyHostToDevice, s), "h2d");
+    hip_check(hipMemcpyAsync(ub + u_c, cid.data(), nu * 4, hipMemcpyHostToDevice, s), "h2d");
+    uint64_t ok = 0;
+    const int rc = stage_update_batch_device(c.stock, (const uint64_t *)(ub + u_k), nullptr, nu, 0, ub + u_d, 16,
+                                             (const uint32_t *)(ub + u_w), (const uint32_t *)(ub + u_c), nullptr,
+                                             ub + u_rc, &ok, s);
+    if (rc) return rc;
+    std::vector<uint8_t> rcs(nu);
+    hip_check(hipMemcpyAsync(rcs.data(), ub + u_rc, nu, hipMemcpyDeviceToHost, s), "d2h");
+    hip_check(hipStreamSynchronize(s), "update sync");
+    for (uint64_t j = 0; j < nu; ++j) recs[ui[j]].update_rc = rcs[j];
+    return STAGE_OK;
+}
+
+static int q2_run(const Q2Call &c) {
+    if (int rc = q2_check(c)) return rc;
+    return guarded([&] {
+        hip_check(hipSetDevice(c.stock->dev.device), "hipSetDevice");
+        hipStream_t s = pick(c.stock, c.stream);
+        const Q2Trace trace;
+        if (!c.async) {
+            *c.n_out = 0;
+            for (uint32_t q = 0; q < c.nq; ++q) c.aborted[q] = 0;
         }
-        if (!launched) enqueue();
-        lap("enqueued");
-        if (async) {  // the results are read by stage_ch_query2_wait
-            if (!P.ev) hip_check(hipEventCreateWithFlags(&P.ev, hipEventDisableTiming), "q2 event");
-            P.split = split;
-            if (split) {  // the records cross PCIe from the side stream while s goes on
-                hip_check(hipEventRecord(P.fin, s), "q2 event");
-                hip_check(hipStreamWaitEvent(stock->q2_side, P.fin, 0), "q2 side wait");
-                // a 2-D copy (the DMA engine) of the expected count's columns -- the last call's
-                // count; wait() copies any more.  (A kernel writing the records over PCIe from the
-                // side stream slowed the next batch's kernels beside it ~4x, 0.153 ms a batch
-                // against 0.127 with the copy, r06q2emit.)
-                P.cols = std::min(n_hint, max_out);
-                if (P.cols)
-                    hip_check(hipMemcpy2DAsync(out, max_out * sizeof(stage_q2_rec), slot_out, n_max * sizeof(stage_q2_rec),
-                                               P.cols * sizeof(stage_q2_rec), nq, hipMemcpyDeviceToHost, stock->q2_side),
-                              "q2 records copy");
-                P.out = out;
-                P.max_out = max_out;
-                P.slot_out = slot_out;
-                hip_check(hipEventRecord(P.ev, stock->q2_side), "q2 event");
-            } else {
-                hip_check(hipEventRecord(P.ev, s), "q2 event");
-            }
-            P.pq = pq;
-            P.q_cn = q_cn;
-            P.q_ab = q_ab;
-            P.nq = nq;
-            P.stream = s;
-            P.n_max = n_max;
-            P.m_max = m_max;
-            P.active = true;
-            return STAGE_OK;
-        }
+        if (c.supplier->dev.view.cap % 64) return fail(STAGE_E_UNSUPPORTED, "SUPPLIER leaves of a multiple of 64 slots");
+        Q2Launch L;  // zeroed, its padding too: its bytes are the graph's key
+        std::memset((void *)&L, 0, sizeof L);
+        Q2Plan &p = L.p;
+        q2_plan(p, c);
+        q2_stage(p, c);
+        trace.lap("staged");
+        q2_bind(p, c);
+        stage_q2_rec *host_out = q2_device_view(c.out, c.max_out);
+        if (Q2Trace::on())
+            std::fprintf(stderr, "[q2] out %s\n", host_out ? "page-locked: written by q2_finish" : "pageable: copied");
+        if (c.async && c.out && c.max_out && !host_out)
+            return fail(STAGE_E_ARG, "stage_ch_query2_batch_async needs a page-locked out (stage_host_alloc)");
+        Q2Pending &P = c.stock->q2p[c.slot];
+        stage_q2_rec *slot_out =
+            c.async && host_out ? q2_slot_buffer(c.stock, P, p.n_max * c.nq * sizeof(stage_q2_rec)) : nullptr;
+        trace.lap("buffers");
+        q2_order(c, s);
+        q2_arguments(L, c, host_out, slot_out, s);
+        const std::string key = q2_key(L, {c.region, c.nation, c.supplier, c.item, c.stock});
+        trace.lap("key");
+        const char *how = replay_or_enqueue(c.stock->q2g[c.slot], key, s, [&L] { q2_enqueue(L); });
+        if (Q2Trace::on()) std::fprintf(stderr, "[q2] batch %s\n", how);
+        trace.lap("enqueued");
+        q2_park(c, L, P);
+        if (c.async) return STAGE_OK;  // the results are read by stage_ch_query2_wait
         hip_check(hipStreamSynchronize(s), "q2 sync");  // the batch's one synchronisation
-        lap("results back");
-        uint64_t cn[2];
-        std::memcpy(cn, pq + q_cn, 16);
-        std::memcpy(aborted, pq + q_ab, 4ull * nq);
-        const uint64_t n = cn[0];
-        if (n > n_max || cn[1] > m_max) throw std::runtime_error("q2: device counts out of range");
-        stock->q2_hint[0] = n;
-        stock->q2_hint[1] = cn[1];
-        *n_out = n;
-        if (n == 0) {
-            for (uint32_t q = 0; q < nq; ++q) aborted[q] = 0;
-            return STAGE_OK;
-        }
+        trace.lap("results back");
+        const uint64_t n = q2_collect(c.stock, P, c.n_out, c.aborted);
+        if (n == 0) return STAGE_OK;
         std::vector<stage_q2_rec> recs_buf;
-        const stage_q2_rec *recs = host_out ? out : nullptr;
         if (!host_out) {  // a pageable (or no) `out`: the records come back now
-            recs_buf.resize(n * nq);
-            hip_check(hipMemcpy(recs_buf.data(), d_rec, n * nq * sizeof(stage_q2_rec), hipMemcpyDeviceToHost), "d2h");
-            recs = recs_buf.data();
+            recs_buf.resize(n * c.nq);
+            hip_check(hipMemcpy(recs_buf.data(), p.d_rec, n * c.nq * sizeof(stage_q2_rec), hipMemcpyDeviceToHost), "d2h");
         }
-        auto rec = [&](uint32_t q, uint64_t k) -> stage_q2_rec & {
-            return host_out ? out[(uint64_t)q * max_out + k] : recs_buf[(uint64_t)q * n + k];
-        };
-        const uint32_t read_id = rq[0];
-        // 5. the transaction's stock updates, through the device write path
-        if (nq == 1 && commit_id && !*aborted) {
-            std::vector<uint64_t> uk;
-            std::vector<int32_t> ud;
-            std::vector<uint32_t> ui;
-            for (uint32_t k = 0; k < n && (!host_out || k < max_out); ++k)
-                if (rec(0, k).update) {
-                    uk.push_back((uint64_t)rec(0, k).s_w_id);
-                    uk.push_back((uint64_t)rec(0, k).s_i_id);
-                    ud.insert(ud.end(), {rec(0, k).s_quantity + 50, rec(0, k).s_ytd, rec(0, k).s_order_cnt,
-                                         rec(0, k).s_remote_cnt});
-                    ui.push_back(k);
-                }
-            const uint64_t nu = ui.size();
-            if (nu) {
-                uint64_t o2 = 0;
-                auto take2 = [&](uint64_t bytes) {
-                    const uint64_t o = o2;
-                    o2 += al(bytes);
-                    return o;
-                };
-                const uint64_t u_k = take2(nu * 16), u_d = take2(nu * 16), u_w = take2(nu * 4), u_c = take2(nu * 4),
-                               u_rc = take2(nu);
-                uint8_t *ub = scratch_bytes(item->dev, o2);
-                std::vector<uint32_t> wid(nu, read_id), cid(nu, commit_id);
-                hip_check(hipMemcpyAsync(ub + u_k, uk.data(), nu * 16, hipMemcpyHostToDevice, s), "h2d");
-                hip_check(hipMemcpyAsync(ub + u_d, ud.data(), nu * 16, hipMemcpyHostToDevice, s), "h2d");
-                hip_check(hipMemcpyAsync(ub + u_w, wid.data(), nu * 4, hipMemcpyHostToDevice, s), "h2d");
-                hip_check(hipMemcpyAsync(ub + u_c, cid.data(), nu * 4, hipMemcpyHostToDevice, s), "h2d");
-                uint64_t ok = 0;
-                const int rc = stage_update_batch_device(stock, (const uint64_t *)(ub + u_k), nullptr, nu, 0,
-                                                         ub + u_d, 16, (const uint32_t *)(ub + u_w),
-                                                         (const uint32_t *)(ub + u_c), nullptr, ub + u_rc, &ok, s);
-                if (rc) return rc;
-                std::vector<uint8_t> rcs(nu);
-                hip_check(hipMemcpyAsync(rcs.data(), ub + u_rc, nu, hipMemcpyDeviceToHost, s), "d2h");
-                hip_check(hipStreamSynchronize(s), "update sync");
-                for (uint64_t j = 0; j < nu; ++j) rec(0, ui[j]).update_rc = rcs[j];
-            }
+        if (c.nq == 1 && c.commit_id && !*c.aborted) {
+            const int rc = host_out ? q2_apply_updates(c, s, c.out, std::min(n, c.max_out))
+                                    : q2_apply_updates(c, s, recs_buf.data(), n);
+            if (rc) return rc;
         }
-        if (!host_out && out)
-            for (uint32_t q = 0; q < nq; ++q)
-                std::memcpy(out + (uint64_t)q * max_out, recs + (uint64_t)q * n,
-                            std::min<uint64_t>(n, max_out) * sizeof(stage_q2_rec));
-        lap("out copied");
+        if (!host_out && c.out)
+            for (uint32_t q = 0; q < c.nq; ++q)
+                std::memcpy(c.out + (uint64_t)q * c.max_out, recs_buf.data() + (uint64_t)q * n,
+                            std::min<uint64_t>(n, c.max_out) * sizeof(stage_q2_rec));
+        trace.lap("out copied");
         return STAGE_OK;
     });
 }
@@ -996,8 +1097,8 @@ extern "C" int stage_ch_query2(stage_table *region, stage_table *nation, stage_t
                                stage_table *stock, const uint32_t *map_off, const uint64_t *d_map_keys,
                                int32_t target_region, uint32_t read_id, uint32_t commit_id, stage_q2_rec *out,
                                uint64_t max_out, uint64_t *n_out, int32_t *aborted, void *stream) {
-    return q2_run(region, nation, supplier, item, stock, map_off, d_map_keys, target_region, &read_id, 1, commit_id,
-                  out, max_out, n_out, aborted, stream);
+    return q2_run({region, nation, supplier, item, stock, map_off, d_map_keys, target_region, &read_id, 1, commit_id,
+                   out, max_out, n_out, aborted, stream, 0, false});
 }
 
 extern "C" int stage_ch_query2_batch_async(stage_table *region, stage_table *nation, stage_table *supplier,
@@ -1007,8 +1108,8 @@ extern "C" int stage_ch_query2_batch_async(stage_table *region, stage_table *nat
                                            void *stream) {
     if (nq == 0 || !read_ids || nq > 4096) return fail(STAGE_E_ARG, "read_ids: 1..4096 queries");
     if (!out || !max_per_query) return fail(STAGE_E_ARG, "an out array is required");
-    return q2_run(region, nation, supplier, item, stock, map_off, d_map_keys, target_region, read_ids, nq, 0, out,
-                  max_per_query, nullptr, nullptr, stream, slot, true);
+    return q2_run({region, nation, supplier, item, stock, map_off, d_map_keys, target_region, read_ids, nq, 0, out,
+                   max_per_query, nullptr, nullptr, stream, slot, true});
 }
 
 extern "C" int stage_ch_query2_wait(stage_table *stock, int slot, uint64_t *n_out, int32_t *aborted) {
@@ -1016,23 +1117,11 @@ extern "C" int stage_ch_query2_wait(stage_table *stock, int slot, uint64_t *n_ou
     Q2Pending &P = stock->q2p[slot];
     if (!P.active) return fail(STAGE_E_STATE, "no CH-Q2 batch in flight in this slot");
     return guarded([&] {
+        // the slot stays busy until its event and its records' rest have come back: while either
+        // fails, a copy out of its buffer may still be queued (~stage_table waits for a busy slot)
+        hip_check(hipEventSynchronize(P.ev), "q2 wait");
+        q2_collect(stock, P, n_out, aborted);
         P.active = false;
-        stage::hip_check(hipEventSynchronize(P.ev), "q2 wait");
-        uint64_t cn[2];
-        std::memcpy(cn, P.pq + P.q_cn, 16);
-        std::memcpy(aborted, P.pq + P.q_ab, 4ull * P.nq);
-        if (cn[0] > P.n_max || cn[1] > P.m_max) throw std::runtime_error("q2: device counts out of range");
-        const uint64_t want = std::min<uint64_t>(cn[0], P.max_out);
-        if (P.split && want > P.cols)  // more records than the copy expected
-            stage::hip_check(hipMemcpy2D(P.out + P.cols, P.max_out * sizeof(stage_q2_rec), P.slot_out + P.cols,
-                                         P.n_max * sizeof(stage_q2_rec), (want - P.cols) * sizeof(stage_q2_rec), P.nq,
-                                         hipMemcpyDeviceToHost),
-                             "q2 records rest");
-        stock->q2_hint[0] = cn[0];
-        stock->q2_hint[1] = cn[1];
-        *n_out = cn[0];
-        if (cn[0] == 0)
-            for (uint32_t q = 0; q < P.nq; ++q) aborted[q] = 0;
         return STAGE_OK;
     });
 }
@@ -1044,8 +1133,8 @@ extern "C" int stage_ch_query2_batch(stage_table *region, stage_table *nation, s
                                      int32_t *aborted, void *stream) {
     if (nq == 0) return STAGE_OK;
     if (!read_ids || nq > 4096) return fail(STAGE_E_ARG, "read_ids: 1..4096 queries");
-    return q2_run(region, nation, supplier, item, stock, map_off, d_map_keys, target_region, read_ids, nq, 0, out,
-                  max_per_query, n_out, aborted, stream);
+    return q2_run({region, nation, supplier, item, stock, map_off, d_map_keys, target_region, read_ids, nq, 0, out,
+                   max_per_query, n_out, aborted, stream, 0, false});
 }
 
 // the multi-table operations' scratch plans (stage_hip.h)

@@ -27,14 +27,18 @@ struct HostPipeDeleter {
 };
 }  // namespace stage
 
-// CH-Q2's captured batch (chq2.hip): replayed while its key -- every argument of the captured
-// launches -- stays the same
+// CH-Q2's captured batch (chq2.hip, replay_or_enqueue): replayed while its key stays the same.
+// The key is the bytes of the one struct the captured launches read their arguments from
+// (Q2Launch, q2_key), so an argument cannot change without the key changing.
 struct Q2Graph {
     hipGraphExec_t exec = nullptr;
-    std::string key, last_key;
-    bool failed = false;
+    std::string key, last_key;  // of `exec`; of the previous call (the same call twice is captured)
+    bool failed = false;        // a capture or instantiation failed: enqueue from then on
 };
-// a CH-Q2 batch enqueued by stage_ch_query2_batch_async and not yet waited for (per slot)
+// Where a CH-Q2 batch's results are, per slot (q2_park fills it, q2_collect reads it).  `active`:
+// enqueued by stage_ch_query2_batch_async and not yet waited for -- the slot's buffers are in use.
+// stage_ch_query2_wait clears it only once the event wait and the records' rest copy succeeded.
+// A synchronous call parks in the idle slot 0 and collects before it returns.
 struct Q2Pending {
     bool active = false;
     hipEvent_t ev = nullptr;  // after the batch's last copy (its records' copy, when split)

@@ -22,6 +22,7 @@
 #include <stdexcept>
 
 #include "handle.hpp"
+#include "tuple_read.hpp"
 
 using namespace stage_capi;
 
@@ -40,17 +41,10 @@ __global__ void sl_district_keys(const int64_t *__restrict__ w, const int64_t *_
     keys[2 * i + 1] = (uint64_t)d[i];
 }
 
-__device__ __forceinline__ int32_t ld_i32(const uint8_t *p) {
-    return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
-}
 __device__ __forceinline__ int64_t ld_i64(const uint8_t *p) {
     uint64_t v = 0;
     for (int b = 0; b < 8; ++b) v |= (uint64_t)p[b] << (8 * b);
     return (int64_t)v;
-}
-
-__device__ __forceinline__ bool produced_tuple(uint32_t st) {
-    return st == ST_LATEST || st == ST_COPY || st == ST_OLD;
 }
 
 __global__ void sl_spread_rids(const uint32_t *__restrict__ rids, uint64_t ns, uint32_t *__restrict__ out) {

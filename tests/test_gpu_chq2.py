@@ -202,6 +202,46 @@ def test_q2_place_forms_agree(ch, monkeypatch):
         assert (ra == rb).all()
 
 
+def test_q2_graph_follows_its_arguments(ch, monkeypatch):
+    """The captured graph of a batch (slot 0: the synchronous calls) is replayed only for the call
+    it was captured from.  The same batch three times (enqueued, captured, replayed -- the first
+    two may both enqueue where the first call's counts change the launch shapes), then one
+    argument changed at a time, three calls each: every call's records and abort flags equal the
+    oracle's, query by query.  A graph replayed after a change would answer the previous call
+    (another target's suppliers, the other `out` left zeroed, fewer or other read ids)."""
+    oracle = {}
+    zero = np.zeros(1, stage.Q2_REC_DTYPE)[0]
+
+    def three_calls(rids, target, out, stream=None):
+        rids = np.array(rids, np.uint32)
+        for rep in range(3):
+            out[...] = zero  # the records must come from this call
+            recs, ab = ch.query2_batch(rids, target, out=out, stream=stream)
+            assert recs.shape[0] == rids.size and np.shares_memory(recs, out)
+            for q, r in enumerate(rids):
+                if (target, int(r)) not in oracle:
+                    oracle[target, int(r)] = ch.query2_oracle(target, int(r))
+                orecs, oab = oracle[target, int(r)]
+                assert ab[q] == oab, (rep, q)
+                if not oab:
+                    same(recs[q], orecs)
+
+    wide = stage.pinned_empty((4, 1 << 14), stage.Q2_REC_DTYPE)
+    narrow = stage.pinned_empty((3, 1 << 12), stage.Q2_REC_DTYPE)
+    pageable = np.zeros((3, 1 << 12), stage.Q2_REC_DTYPE)
+    s = stage.Stream()
+    three_calls([0xFFFFFFFE, 25, 60, 40], 3, wide)
+    three_calls([0xFFFFFFFE, 25, 60], 3, wide[:3])  # the number of read ids
+    three_calls([60, 0xFFFFFFFE, 3], 3, wide[:3])  # their values
+    three_calls([60, 0xFFFFFFFE, 3], 0, wide[:3])  # the target
+    three_calls([60, 0xFFFFFFFE, 3], 0, narrow)  # a page-locked `out` of another width
+    three_calls([60, 0xFFFFFFFE, 3], 0, pageable)  # a pageable `out` ...
+    three_calls([60, 0xFFFFFFFE, 3], 0, narrow)  # ... and a page-locked one again
+    three_calls([60, 0xFFFFFFFE, 3], 0, narrow, stream=s.ptr)  # the stream
+    monkeypatch.setenv("STAGE_Q2_PLACE_CHUNKS", "0")  # the three-kernel placement
+    three_calls([60, 0xFFFFFFFE, 3], 0, narrow, stream=s.ptr)
+
+
 def test_q2_batches_on_different_streams(ch):
     """The two async slots and a synchronous batch share the tables' device scratch:
     batches enqueued on different streams while another is in flight wait for it on the device,
